@@ -9,9 +9,12 @@ host memory. The defaults time 20 x 5,120 = 102,400 permutations per GPU:
 the metric's nPerm = 100k. Inputs (test corr, net, scaled data, discovery
 vectors) are resident in HBM before the timed region.
 
-A secondary record times the network-only path on the same 20k-gene
-matrices (BASELINE.json configs[3], C4: the HBM-bound gather kernel) in the
-same run.
+A plain run sets up, warms up, times the steps and prints the result line;
+`--dump-outputs DIR` also writes the null cube of the last timed step to
+DIR/nulls.npy. With `--full` the same run goes on to a secondary record that
+times the network-only path on the same 20k-gene matrices (BASELINE.json
+configs[3], C4: the HBM-bound gather kernel) and to the CPU baseline sample
+(`cpu_baseline`); both are null in a plain run's line.
 
 Multi-GPU: one process per GPU. `--gpus N` without a torchrun environment
 re-launches this script under torch.distributed.run with N processes before
@@ -128,11 +131,18 @@ def parse():
                          "1,024 / 2,048 / 4,096 measured 12,237 / 12,319 / 12,340 perms/s, "
                          "profiles/r02/batch/)")
     ap.add_argument("--config", default="C3", choices=["C2", "C3", "C4", "C5"])
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C4 network-only record")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: the C4 "
+                         "network-only record, the CPU baseline sample and, at C5, upload and compute alone "
+                         "with their per-kernel figures")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the null cube of the last timed step (the arrays nr_run / PermutationProcedure "
+                         "returned) as DIR/<name>.npy")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the C4 network-only record")
     ap.add_argument("--secondary-steps", type=int, default=8)
     ap.add_argument("--cpu-baseline-perms", type=int, default=0,
                     help="CPU sample size (0: sized for ~15 s on the host cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline sample")
     ap.add_argument("--lib", default=None,
                     help="tuning A/B only: another build of libnetrep_amd.so (make OUT=... EXTRA=-D...)")
     ap.add_argument("--seed", type=int, default=0x5EED)
@@ -330,6 +340,26 @@ def time_steps(eng, world, rank, steps, warmup, perms_per_step, seed, base_warm)
     return elapsed, chunks, total
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, arrays, seed):
+    """--dump-outputs: each array of the last timed step as out_dir/<name>.npy
+    (float64, as the engine returns them). Arrays that together exceed 64 MB
+    are cut to a fixed sample of their last (permutation) axis, drawn from
+    `seed` and kept in ascending order, so two builds write the same cells."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes < 2**20)   # written whole
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if total > DUMP_LIMIT_BYTES and a.nbytes >= 2**20:
+            keep = max(1, int(a.shape[-1] * (DUMP_LIMIT_BYTES - small) / (total - small)))
+            rng = np.random.default_rng(seed)
+            a = a[..., np.sort(rng.choice(a.shape[-1], keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def host_cores():
     """The host CPU as this process sees it: the machine's logical CPUs
     (nproc), the ones this process may run on (affinity), the CPU model, and
@@ -457,6 +487,7 @@ def run_c5(args, world, rank, local):
     order = [(k_, t) for k_ in range(-W, K) for t in range(3)]
     N.PrefetchTestDataset(*datasets[0])
     call_s = []
+    last_step = {}   # test dataset -> what its call of the last timed step returned
     t0 = None
     for i, (k_, t) in enumerate(order):
         if k_ == 0 and t == 0:
@@ -469,11 +500,42 @@ def run_c5(args, world, rank, local):
                                       seed=seed + 1000 * k_ + t)
         if k_ >= 0:
             call_s.append(round(time.perf_counter() - tc_, 4))
+        if k_ == K - 1:
+            last_step[t] = last
     elapsed = time.perf_counter() - t0
     finite = float(np.isfinite(last["nulls"]).mean())
-    # upload alone (pinned double-buffered chunks, 25.9 GB per dataset) and
-    # compute alone (dataset resident) on one dataset, engine layer
-    x, c, nt = datasets[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     {f"{key}_dataset{t}": r[key] for t, r in sorted(last_step.items())
+                      for key in ("nulls", "observed")}, seed)
+    total = 3 * P * K
+    line = {
+        "metric": f"permutations/sec (whole node), {n // 1000}k genes x {len(sizes)} modules, 3 test datasets",
+        "value": total / elapsed, "unit": "permutations/sec", "n_gpus": 1, "steps": K, "warmup": W,
+        "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic coexpression (SURVEY.md 8d generator), random module layout",
+        "config": {"workload": f"C5: {n} genes x {s} samples, {len(sizes)} modules ({min(sizes)}-{max(sizes)} genes, "
+                               f"discovery over {n_disc} genes), 3 test datasets of {n} genes each in host memory, "
+                               f"null=all (pool = the {n} test genes), 7 statistics, "
+                               f"netrep_PermutationProcedure per dataset with netrep_PrefetchTestDataset",
+                   "perms_per_step": 3 * P, "perms_per_dataset_per_step": P, "parallelism": "perm-shard x1"},
+        "pipelined_s_per_dataset": elapsed / (3 * K),
+        "call_s": call_s,
+        "finite_fraction": finite, "setup_s": t_setup, "full": args.full, "cpu_baseline": None,
+    }
+    if args.full:
+        line.update(c5_alone(args, local, datasets[0], lay_d, d_names, modules, node_off, v, P))
+    print(json.dumps(line))
+
+
+def c5_alone(args, local, dataset, lay_d, d_names, modules, node_off, v, P):
+    """--full at C5: upload alone (pinned double-buffered chunks, 25.9 GB per
+    dataset) and compute alone (dataset resident) on one dataset, engine
+    layer, with the per-kernel figures of that run and the CPU baseline
+    sample; returns the fields they add to the result line."""
+    n, s, sizes, _, _ = S.CONFIGS["C5"]
+    seed = args.seed
+    x, c, nt = dataset
     e2 = N.Engine(local)
     t1 = time.perf_counter()
     e2.set_dataset(c.f, nt.f, x.f)
@@ -497,28 +559,16 @@ def run_c5(args, world, rank, local):
     diag = e2.diagnostics()
     e2.close()
     _, prof_b, prof_f = roofline_terms(sizes, s, True)
-    total = 3 * P * K
     line = {
-        "metric": f"permutations/sec (whole node), {n // 1000}k genes x {len(sizes)} modules, 3 test datasets",
-        "value": total / elapsed, "unit": "permutations/sec", "n_gpus": 1, "steps": K, "warmup": W,
-        "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic coexpression (SURVEY.md 8d generator), random module layout",
-        "config": {"workload": f"C5: {n} genes x {s} samples, {len(sizes)} modules ({min(sizes)}-{max(sizes)} genes, "
-                               f"discovery over {n_disc} genes), 3 test datasets of {n} genes each in host memory, "
-                               f"null=all (pool = the {n} test genes), 7 statistics, "
-                               f"netrep_PermutationProcedure per dataset with netrep_PrefetchTestDataset",
-                   "perms_per_step": 3 * P, "perms_per_dataset_per_step": P, "parallelism": "perm-shard x1"},
         "upload_s_per_dataset": upload_s,
         "upload_GBps": (2 * n * n + s * n) * 8 / upload_s / 1e9,
         "compute_s_per_dataset": compute_s,
         "compute_perms_per_sec": P / compute_s,
-        "pipelined_s_per_dataset": elapsed / (3 * K),
-        "call_s": call_s,
         "kernels": {NET_KERNEL: {"avg_ms": ms0 / max(l0, 1), "launches": l0},
                     "module_profile_kernel": {"avg_ms": ms1 / max(l1, 1), "launches": l1,
                                               "achieved": prof_f * P / (ms1 * 1e-3) / 1e12 if ms1 > 0 else None,
                                               "peak": FP64_MFMA_PEAK_TFS, "unit": "TFLOP/s"}},
-        "finite_fraction": finite, "setup_s": t_setup, "eigen_diagnostics": diag,
+        "eigen_diagnostics": diag,
     }
     mk = line["kernels"]["module_profile_kernel"]
     if mk["achieved"] is not None:
@@ -559,7 +609,7 @@ def run_c5(args, world, rank, local):
                "sample": f"{n_cpu} permutations x {len(modules)} modules of test dataset 0 in {dt:.1f} s: C++ "
                          f"restatement of src/permutations.cpp (std::thread chunks, LAPACK SVD), {threads} threads"}
     line["cpu_baseline"] = cpu
-    print(json.dumps(line))
+    return line
 
 
 def main():
@@ -579,7 +629,7 @@ def main():
     n_cfg, s_cfg, sizes_cfg, _, _ = S.CONFIGS[args.config]
 
     eng2 = None
-    if not args.no_secondary and meta["with_data"] and args.config == "C3":
+    if args.full and not args.no_secondary and meta["with_data"] and args.config == "C3":
         eng2 = secondary_engine(local, meta, tensors)
     host = tensors if (rank == 0 and world == 1) else None
     if host is None:
@@ -598,6 +648,12 @@ def main():
     del chunks
     cube = gather_nulls(local_cube, rank, world, total_perms) if world > 1 else local_cube
     finite = float(np.isfinite(cube).mean()) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        # the last timed step of every rank (a rank's chunk is K * P contiguous
+        # permutations of the gathered cube), in rank order
+        last = [cube[:, :, (r + 1) * K * P - P:(r + 1) * K * P] for r in range(world)]
+        dump_outputs(args.dump_outputs, {"nulls": np.concatenate(last, axis=2)}, args.seed)
+        del last
     del cube, local_cube
 
     # -- secondary record: network-only (C4) on the same matrices ---------------
@@ -700,7 +756,7 @@ def main():
                 roofline[key] = dom[key]
         roofline["executed"] = measured_mfma(args.config, B, dom_name, dom["avg_ms"], bool(table))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and host is not None:
+        if args.full and world == 1 and not args.no_cpu_baseline and host is not None:
             rate, dt, n_cpu, threads, hc = cpu_baseline(lay, meta, host, args.cpu_baseline_perms, args.seed)
             cpu = {"value": rate, "unit": "permutations/sec", "cores": threads, "kind": "port",
                    "per_core": rate / threads,
@@ -744,6 +800,7 @@ def main():
             "kernels": kernels,
             "cpu_baseline": cpu,
             "secondary": secondary,
+            "full": args.full,
             "finite_fraction": finite,
             "broadcast_s": meta["t_bcast"],
             "symmetric_matrices": meta["symmetric"],

@@ -15,6 +15,38 @@ def test_gpus_mismatch_with_torchrun_env_fails():
     assert r.returncode == 2 and "WORLD_SIZE=3" in r.stderr
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full (secondary record, CPU baseline) is off unless asked for."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_outputs_is_capped_and_repeatable(tmp_path):
+    """Small arrays are written whole; beyond 64 MB in all the large ones
+    keep a seeded, ordered sample of their permutation axis."""
+    import numpy as np
+    import bench
+    cube = np.arange(50 * 7 * 30000, dtype=np.float64).reshape(50, 7, 30000)   # 84 MB
+    obs = np.arange(350, dtype=np.float64).reshape(50, 7)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"nulls": cube, "observed": obs}, 7)
+    a, b = np.load(tmp_path / "a" / "nulls.npy"), np.load(tmp_path / "b" / "nulls.npy")
+    np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "observed.npy"), obs)
+    assert a.dtype == np.float64 and a.shape[:2] == (50, 7) and 1 < a.shape[2] < 30000
+    assert a.nbytes + obs.nbytes <= 64 * 2**20
+    cols = a[0, 0].astype(np.int64)                       # cube[0, 0, j] == j
+    assert (np.diff(cols) > 0).all()
+    np.testing.assert_array_equal(a, cube[:, :, cols])
+    bench.dump_outputs(str(tmp_path / "c"), {"nulls": cube[:, :, :5120]}, 7)
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "nulls.npy"), cube[:, :, :5120])
+
+
 def test_relaunch_command_is_torchrun(monkeypatch):
     import bench
     calls = {}

@@ -9,11 +9,11 @@ export TMPDIR=/tmp
 run() {  # name, counters...
   local name=$1; shift
   timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -o run -- \
-      python3 bench.py --no-cpu-baseline "${BENCH_ARGS[@]}" > "$out/$name.log" 2>&1 || return 1
+      python3 bench.py --full --no-cpu-baseline "${BENCH_ARGS[@]}" > "$out/$name.log" 2>&1 || return 1
 }
 BENCH_ARGS=("$@")
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- \
-    python3 bench.py --no-cpu-baseline "${BENCH_ARGS[@]}" > "$out/trace.log" 2>&1 || exit 1
+    python3 bench.py --full --no-cpu-baseline "${BENCH_ARGS[@]}" > "$out/trace.log" 2>&1 || exit 1
 run fetch FETCH_SIZE || exit 1
 run write WRITE_SIZE || exit 1
 run tcc TCC_HIT_sum TCC_MISS_sum || exit 1
