@@ -69,6 +69,39 @@ int nr_set_dataset(nr_ctx* ctx, const double* corr, const double* net,
 #define NR_SCALE_DATA 1
 int nr_set_dataset_ex(nr_ctx* ctx, const double* corr, const double* net,
                       const double* data, int64_t n_nodes, int64_t n_samples, int where, int flags);
+/* The from-data path: the resident dataset made from the data matrix alone,
+ * as NetRep users derive the other two from it (R/example-data.R:111-116:
+ * cor(data), abs(correlation)^5). Only `data` (n_samples x n_nodes) is
+ * uploaded (flags: NR_SCALE_DATA = unscaled, scaled on the device; 0 = already
+ * scaled as by Scale); a lower-triangle SYRK on the fp64 matrix cores then
+ * writes the {corr, net} pairs in place:
+ *   corr(i,j) = clamp(x_i . x_j / (n_samples - 1), -1, 1)   (R's cor clamps)
+ *   net(i,j)  = |corr|^beta                  NR_NET_UNSIGNED
+ *               ((1 + corr) / 2)^beta        NR_NET_SIGNED
+ *               corr > 0 ? corr^beta : 0     NR_NET_SIGNED_HYBRID
+ * with NaN propagating through all three. Every tile is stored at (i, j) and,
+ * the same bits, at (j, i): the matrices are exactly symmetric by
+ * construction (no symmetry pass), and nr_dataset_finite reports what the
+ * kernel's epilogue saw (a constant column gives NaN, as R's cor gives NA).
+ * Everything downstream (modules, observed, run, Gram table, broadcast) runs
+ * on the dataset unchanged. NR_ERR_INVALID before anything touches the GPU:
+ * data == NULL, n_samples < 2, n_nodes < 1, an unknown net_type or flag, beta
+ * not finite or <= 0. `where` as nr_set_dataset. */
+#define NR_NET_UNSIGNED 0
+#define NR_NET_SIGNED 1
+#define NR_NET_SIGNED_HYBRID 2
+int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples,
+                             int where, int flags, int net_type, double beta);
+/* Device time in ms (HIP events on the context's stream) of the kernel that
+ * built the resident dataset's matrices from its data; 0 for a dataset made
+ * any other way. */
+int nr_netbuild_ms(nr_ctx* ctx, double* ms);
+/* The resident corr and net (n_nodes x n_nodes each, column-major) to host
+ * arrays; either may be NULL. Works for a dataset made by any of the
+ * set-dataset calls, before or after the Gram table is built: the pairs are
+ * split on the device into a bounded staging buffer and copied out in chunks. */
+int nr_get_dataset_matrices(nr_ctx* ctx, double* corr_out, double* net_out);
+
 /* Drop the resident dataset (and modules / null pool bound to it); the
  * context keeps its streams and scratch for the next dataset. */
 int nr_clear_dataset(nr_ctx* ctx);
@@ -388,6 +421,30 @@ int netrep_PermutationProcedureFiles(const netrep_disc_props* disc_props, const 
                                      int64_t n_perm, int32_t n_cores, const char* null_hypothesis,
                                      int32_t verbose, uint64_t seed, const uint32_t* pi, int64_t pi_len,
                                      double* nulls_out, double* observed_out);
+
+/* PermutationProcedure with the test dataset given as its data matrix alone
+ * (nr_set_dataset_from_data on GPU 0: t_data is uploaded, scaled there when
+ * scale_data != 0, and the correlation and network are built in HBM from it
+ * by net_type (NR_NET_*) and beta; no n x n host matrix exists or crosses
+ * PCIe). Built matrices that are not all finite -- a constant column, for
+ * which R's cor gives NA -- return NR_ERR_NONFINITE with CheckFinite's
+ * message before any permutation runs (the reference stops such input in
+ * R/check-user-input.R:796-799). Other arguments, outputs, multi-GPU
+ * broadcast, progress, interrupt and the NR_ERR_OOM retry as
+ * netrep_PermutationProcedure. */
+int netrep_PermutationProcedureFromData(
+    const netrep_disc_props* disc_props, const double* t_data, int32_t scale_data, int32_t net_type,
+    double beta, int64_t n_samples, int64_t n_nodes, const char* const* t_names,
+    const char* const* ma_names, const char* const* ma_labels, int64_t n_assign,
+    const char* const* modules, int64_t n_modules, int64_t n_perm, int32_t n_cores,
+    const char* null_hypothesis, int32_t verbose, uint64_t seed, const uint32_t* pi,
+    double* nulls_out, double* observed_out);
+
+/* The same build, copied back: corr_out and net_out (n_nodes x n_nodes each,
+ * either may be NULL) for callers who still need host matrices, e.g. for the
+ * discovery-side calls. Non-finite results are returned as they are. */
+int netrep_BuildNetwork(const double* data, int32_t scale_data, int32_t net_type, double beta,
+                        int64_t n_samples, int64_t n_nodes, double* corr_out, double* net_out);
 
 /* Host read of one numeric matrix from an RDS file or save() archive (the
  * same reader): dims always; values (column-major, native) into `out` when

@@ -11,6 +11,7 @@ from ._lib import NetRepError, load  # noqa: F401
 from .api import (CheckFinite, IntermediateProperties, IntermediatePropertiesNoData,  # noqa: F401
                   NetProps, NetPropsNoData, PermutationProcedure, PermutationProcedureNoData,
                   PrefetchTestDataset, DiscardPrefetch, ReleaseResident, h2d_bytes, PermutationProcedureFiles, RMatrix,
+                  PermutationProcedureFromData, BuildNetwork,
                   read_rds_matrix, Scale, STATNAMES, STATNAMES_NODATA,
                   set_interrupt_hook)
 from .engine import Engine, device_count, prp_table  # noqa: F401
@@ -19,4 +20,5 @@ __all__ = ["CheckFinite", "IntermediateProperties", "IntermediatePropertiesNoDat
            "NetPropsNoData", "PermutationProcedure", "PermutationProcedureNoData", "RMatrix",
            "Scale", "Engine", "NetRepError", "device_count", "prp_table", "STATNAMES",
            "STATNAMES_NODATA", "set_interrupt_hook", "PrefetchTestDataset",
-           "DiscardPrefetch", "ReleaseResident", "h2d_bytes", "PermutationProcedureFiles", "read_rds_matrix"]
+           "DiscardPrefetch", "ReleaseResident", "h2d_bytes", "PermutationProcedureFiles", "read_rds_matrix",
+           "PermutationProcedureFromData", "BuildNetwork"]

@@ -26,6 +26,12 @@ NR_ERR_NONFINITE = 6
 NR_HOST = 0
 NR_DEVICE = 1
 NR_SCALE_DATA = 1
+NR_NET_UNSIGNED = 0
+NR_NET_SIGNED = 1
+NR_NET_SIGNED_HYBRID = 2
+# networkType names of the from-data entries (WGCNA's spelling accepted too)
+NET_TYPES = {"unsigned": NR_NET_UNSIGNED, "signed": NR_NET_SIGNED, "signed_hybrid": NR_NET_SIGNED_HYBRID,
+             "signed hybrid": NR_NET_SIGNED_HYBRID}
 
 
 class NetRepError(RuntimeError):
@@ -129,6 +135,13 @@ SIGNATURES = {
     "nr_debug_set": (_int, [_int, _i64]),
     "nr_peer_staged_pairs": (_int, [_intp]),
     "netrep_PoolInfo": (_int, [_i64p, _i64p, _i32p, _i32p]),
+    "nr_set_dataset_from_data": (_int, [_p, _dp, _i64, _i64, _int, _int, _int, C.c_double]),
+    "nr_netbuild_ms": (_int, [_p, C.POINTER(C.c_double)]),
+    "nr_get_dataset_matrices": (_int, [_p, _dp, _dp]),
+    "netrep_PermutationProcedureFromData": (_int, [C.POINTER(DiscProps), _dp, _i32, _i32, C.c_double, _i64, _i64,
+                                                   _strv, _strv, _strv, _i64, _strv, _i64, _i64, _i32, C.c_char_p,
+                                                   _i32, _u64, _u32p, _dp, _dp]),
+    "netrep_BuildNetwork": (_int, [_dp, _i32, _i32, C.c_double, _i64, _i64, _dp, _dp]),
 }
 NR_DEBUG_SWEEP_MAX_OCC = 1
 NR_DEBUG_FAIL_SWEEP_ALLOC = 2
@@ -170,6 +183,15 @@ def load() -> C.CDLL:
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def net_type_code(network_type) -> int:
+    """NR_NET_* of a networkType name."""
+    key = str(network_type).lower().replace("-", "_")
+    if key not in NET_TYPES:
+        raise NetRepError(NR_ERR_INVALID, f"unknown networkType {network_type!r}: one of "
+                                          "'unsigned', 'signed', 'signed_hybrid'")
+    return NET_TYPES[key]
 
 
 def check(rc: int, ctx=None) -> None:

@@ -286,23 +286,10 @@ def h2d_bytes() -> int:
     return int(v.value)
 
 
-def _permutation(disc_props, t_data, t_corr, t_net, module_assignments, modules, n_perm, n_cores,
-                 null_hypothesis, verbose, seed, pi):
-    lib = L.load()
-    names, labels = _assignments(module_assignments)
-    modules = [str(m) for m in modules]
-    with_data = t_data is not None
-    t_names = list(t_net.colnames)
-    n = len(t_names)
-    key = _prefetch_key(t_data, t_corr, t_net)
-    pre = next((p for p in _prefetched if p[0] == key), None)
-    if pre is not None:
-        _prefetched.remove(pre)
-        data, corr, net = pre[1]   # the very arrays the upload read (same pointers)
-    else:
-        corr, net = t_corr.f, t_net.f
-        data = t_data.f if with_data else None
-    s = data.shape[0] if with_data else 0
+def _marshal_disc_props(disc_props, modules, with_data):
+    """netrep_disc_props of a discProps dict ({"degree" | "corr" | "contribution":
+    {module: vector}}) in `modules` order, and the arrays its pointers refer to
+    (keep them alive across the call)."""
     nm_ = len(modules)
     keep = []
 
@@ -324,6 +311,45 @@ def _permutation(disc_props, t_data, t_corr, t_net, module_assignments, modules,
     dp.corr, dp.corr_len = vecs("corr")
     if with_data:
         dp.contribution, dp.contribution_len = vecs("contribution")
+    return dp, keep
+
+
+def _permutation_result(rc, modules, with_data, observed, nulls, n_perm):
+    """The PermutationProcedure list of an entry's return code and outputs; an
+    interrupted run returns the partial, NA-padded cube
+    (src/permutations.cpp:375-408)."""
+    interrupted = rc == L.NR_ERR_CANCELLED
+    if not interrupted:
+        L.check_api(rc)
+    statnames = STATNAMES if with_data else STATNAMES_NODATA
+    res = {"observed": observed, "observed_dimnames": (modules, statnames)}
+    if interrupted:
+        res["interrupted"] = True
+    if n_perm > 0:
+        res["nulls"] = nulls
+        res["nulls_dimnames"] = (modules, statnames, None)  # "permutation.i" left implicit
+    return res
+
+
+def _permutation(disc_props, t_data, t_corr, t_net, module_assignments, modules, n_perm, n_cores,
+                 null_hypothesis, verbose, seed, pi):
+    lib = L.load()
+    names, labels = _assignments(module_assignments)
+    modules = [str(m) for m in modules]
+    with_data = t_data is not None
+    t_names = list(t_net.colnames)
+    n = len(t_names)
+    key = _prefetch_key(t_data, t_corr, t_net)
+    pre = next((p for p in _prefetched if p[0] == key), None)
+    if pre is not None:
+        _prefetched.remove(pre)
+        data, corr, net = pre[1]   # the very arrays the upload read (same pointers)
+    else:
+        corr, net = t_corr.f, t_net.f
+        data = t_data.f if with_data else None
+    s = data.shape[0] if with_data else 0
+    nm_ = len(modules)
+    dp, _keep = _marshal_disc_props(disc_props, modules, with_data)
     n_stat = 7 if with_data else 4
     observed = np.empty((nm_, n_stat), order="F")
     nulls = np.empty((nm_, n_stat, int(n_perm)), order="F") if n_perm > 0 else None
@@ -345,18 +371,7 @@ def _permutation(disc_props, t_data, t_corr, t_net, module_assignments, modules,
         int(n_perm), int(n_cores), str(null_hypothesis).encode(), int(bool(verbose)),
         int(seed) & (2**64 - 1), pi_arr.ctypes.data_as(C.POINTER(C.c_uint32)) if pi_arr is not None else None,
         _dptr(nulls), _dptr(observed))
-    interrupted = rc == L.NR_ERR_CANCELLED
-    if not interrupted:
-        L.check_api(rc)
-    statnames = STATNAMES if with_data else STATNAMES_NODATA
-    res = {"observed": observed, "observed_dimnames": (modules, statnames)}
-    if interrupted:
-        # the reference returns the partial, NA-padded cube (src/permutations.cpp:375-408)
-        res["interrupted"] = True
-    if n_perm > 0:
-        res["nulls"] = nulls
-        res["nulls_dimnames"] = (modules, statnames, None)  # "permutation.i" left implicit
-    return res
+    return _permutation_result(rc, modules, with_data, observed, nulls, n_perm)
 
 
 def PermutationProcedure(discProps: dict, tData: RMatrix, tCorr: RMatrix, tNet: RMatrix,
@@ -403,26 +418,7 @@ def PermutationProcedureFiles(discProps: dict, tData_file: Optional[str], tCorr_
     modules = [str(m) for m in modules]
     with_data = tData_file is not None
     nm_ = len(modules)
-    keep = []
-
-    def vecs(key):
-        d = discProps.get(key, {}) if discProps is not None else {}
-        ptrs = (C.POINTER(C.c_double) * max(nm_, 1))()
-        lens = np.zeros(max(nm_, 1), dtype=np.int64)
-        for i, m in enumerate(modules):
-            if m in d:
-                v = np.ascontiguousarray(d[m], dtype=np.float64)
-                keep.append(v)
-                ptrs[i] = _dptr(v)
-                lens[i] = v.size
-        keep.append(lens)
-        return ptrs, lens.ctypes.data_as(C.POINTER(C.c_int64))
-
-    dp = L.DiscProps()
-    dp.degree, dp.degree_len = vecs("degree")
-    dp.corr, dp.corr_len = vecs("corr")
-    if with_data:
-        dp.contribution, dp.contribution_len = vecs("contribution")
+    dp, _keep = _marshal_disc_props(discProps, modules, with_data)
     n_stat = 7 if with_data else 4
     observed = np.empty((nm_, n_stat), order="F")
     nulls = np.empty((nm_, n_stat, int(nPermutations)), order="F") if nPermutations > 0 else None
@@ -442,17 +438,70 @@ def PermutationProcedureFiles(discProps: dict, tData_file: Optional[str], tCorr_
         int(nPermutations), int(nCores), str(nullHypothesis).encode(), int(bool(verbose)),
         int(seed) & (2**64 - 1), pi_arr.ctypes.data_as(C.POINTER(C.c_uint32)) if pi_arr is not None else None,
         int(pi_arr.size) if pi_arr is not None else -1, _dptr(nulls), _dptr(observed))
-    interrupted = rc == L.NR_ERR_CANCELLED
-    if not interrupted:
-        L.check_api(rc)
-    statnames = STATNAMES if with_data else STATNAMES_NODATA
-    res = {"observed": observed, "observed_dimnames": (modules, statnames)}
-    if interrupted:
-        res["interrupted"] = True
-    if nPermutations > 0:
-        res["nulls"] = nulls
-        res["nulls_dimnames"] = (modules, statnames, None)
-    return res
+    return _permutation_result(rc, modules, with_data, observed, nulls, nPermutations)
+
+
+def PermutationProcedureFromData(discProps: dict, tData: RMatrix, beta: float, moduleAssignments, modules,
+                                 nPermutations: int, nCores: int = 1, nullHypothesis: str = "overlap",
+                                 verbose: bool = False, seed: int = DEFAULT_SEED, pi=None,
+                                 networkType: str = "unsigned", scaleData: bool = False) -> dict:
+    """PermutationProcedure on a test dataset given as its data matrix alone
+    (netrep_PermutationProcedureFromData): ``tData`` (samples x nodes, its
+    colnames the node names; scaled already unless ``scaleData``) is the only
+    upload, and the test correlation (cor(tData)) and network (``networkType``
+    'unsigned' |cor|^beta, 'signed' ((1 + cor) / 2)^beta, 'signed_hybrid'
+    cor^beta where cor > 0, else 0) are built on the GPU. Raises
+    ``NetRepError`` (``NR_ERR_NONFINITE``) if they are not all finite, e.g.
+    for a constant column."""
+    lib = L.load()
+    names, labels = _assignments(moduleAssignments)
+    modules = [str(m) for m in modules]
+    if tData.colnames is None:
+        raise L.NetRepError(L.NR_ERR_INVALID, "tData needs colnames (the node names)")
+    t_names = list(tData.colnames)
+    data = tData.f
+    s, n = data.shape
+    if len(t_names) != n:
+        raise L.NetRepError(L.NR_ERR_INVALID, "tData must have one colname per column")
+    nm_ = len(modules)
+    dp, _keep = _marshal_disc_props(discProps, modules, True)
+    observed = np.empty((nm_, 7), order="F")
+    nulls = np.empty((nm_, 7, int(nPermutations)), order="F") if nPermutations > 0 else None
+    pi_arr = None
+    if pi is not None:
+        pi_arr = np.ascontiguousarray(pi, dtype=np.uint32)
+        n_null = _null_pool_size(names, t_names, nullHypothesis)
+        if pi_arr.ndim != 2 or pi_arr.shape != (int(nPermutations), n_null):
+            raise L.NetRepError(L.NR_ERR_INVALID, f"pi must have shape (nPermutations, n_null) = "
+                                                  f"({int(nPermutations)}, {n_null}), got {pi_arr.shape}")
+    tn, _k1 = _strv(t_names)
+    an, _k2 = _strv(names)
+    al, _k3 = _strv(labels)
+    mo, _k4 = _strv(modules)
+    if verbose and not _progress_user_set:
+        _install_progress(_print_progress)
+    rc = lib.netrep_PermutationProcedureFromData(
+        C.byref(dp), _dptr(data), int(bool(scaleData)), L.net_type_code(networkType), float(beta), s, n, tn, an,
+        al, len(names), mo, nm_, int(nPermutations), int(nCores), str(nullHypothesis).encode(),
+        int(bool(verbose)), int(seed) & (2**64 - 1),
+        pi_arr.ctypes.data_as(C.POINTER(C.c_uint32)) if pi_arr is not None else None, _dptr(nulls),
+        _dptr(observed))
+    return _permutation_result(rc, modules, True, observed, nulls, nPermutations)
+
+
+def BuildNetwork(data, beta: float, networkType: str = "unsigned", scaleData: bool = True):
+    """(correlation, network) of a data matrix, built on the GPU as the from-data
+    path builds them (netrep_BuildNetwork) and copied back, for callers who
+    still need host matrices (the discovery-side calls). ``data`` is raw
+    unless ``scaleData=False``. Node names: the data's colnames."""
+    m = data if isinstance(data, RMatrix) else RMatrix(np.asarray(data))
+    x = m.f
+    s, n = x.shape
+    corr = np.empty((n, n), order="F")
+    net = np.empty((n, n), order="F")
+    L.check_api(L.load().netrep_BuildNetwork(_dptr(x), int(bool(scaleData)), L.net_type_code(networkType),
+                                             float(beta), s, n, _dptr(corr), _dptr(net)))
+    return RMatrix(corr, m.colnames, m.colnames), RMatrix(net, m.colnames, m.colnames)
 
 
 def PermutationProcedureNoData(discProps: dict, tCorr: RMatrix, tNet: RMatrix, moduleAssignments,

@@ -60,6 +60,7 @@ struct nr_ctx {
   double* d_colsum = nullptr;    // [n_nodes] column sums of the data (Gram table)
   int64_t table_checked = -1;    // modules_serial the Gram-table decision was made for
   double table_ms = 0.0;         // wall time of the last Gram-table build
+  double netbuild_ms = 0.0;      // device time of the from-data build of the matrices (0: not built from data)
   double* d_data = nullptr;
   int64_t n_nodes = 0, n_samples = 0;
   std::vector<std::string> node_names;  // column names of a dataset loaded from files
@@ -264,6 +265,7 @@ void reset_dataset(nr_ctx* ctx) {
   dfree(ctx->d_colsum);
   ctx->pairs_es = 1;
   ctx->table_checked = -1;
+  ctx->netbuild_ms = 0.0;
   ctx->node_names.clear();
   ctx->n_nodes = 0;
   ctx->n_samples = 0;
@@ -1403,6 +1405,126 @@ int set_dataset_impl(nr_ctx* ctx, const double* corr, const double* net, const d
   return NR_OK;
 }
 }  // namespace
+
+// ---- the from-data path ---------------------------------------------------
+
+namespace {
+int set_dataset_from_data_impl(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples, int where,
+                               int flags, int net_type, double beta) {
+  const size_t pair_bytes = (size_t)n_nodes * (size_t)n_nodes * sizeof(double2);
+  if (hipMalloc((void**)&ctx->d_pairs, pair_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    ctx->d_pairs = nullptr;
+    return fail(ctx, NR_ERR_OOM,
+                "from-data dataset: allocation of the " + std::to_string(pair_bytes >> 20) +
+                    " MiB {corr, net} array failed (16 bytes per matrix element)");
+  }
+  const size_t bytes = (size_t)(n_samples * n_nodes) * sizeof(double);
+  NR_HIP(ctx, hipMalloc((void**)&ctx->d_data, bytes + 2 * (size_t)n_samples * sizeof(double)));
+  if (int rc = fill_virtual_columns(ctx, n_nodes, n_samples)) return rc;
+  double* raw = nullptr;
+  if (flags & NR_SCALE_DATA) NR_HIP(ctx, hipMalloc((void**)&raw, bytes));
+  double* dst = raw ? raw : ctx->d_data;
+  int rc = NR_OK;
+  if (where == NR_DEVICE) {
+    const hipError_t e = hipMemcpyAsync(dst, data, bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) rc = hip_fail(ctx, e, "data copy");
+  } else {
+    rc = upload_pinned(ctx, data, nullptr, n_samples * n_nodes, nullptr, dst, ctx->stream);
+  }
+  if (!rc && raw) {
+    hipError_t e = nr::launch_scale(raw, ctx->d_data, n_samples, n_nodes, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = hip_fail(ctx, e, "scale");
+  }
+  if (raw) (void)hipFree(raw);
+  if (rc) return rc;
+
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  hipError_t e = hipEventCreate(&ev[0]);
+  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
+  int bad = 0;
+  float ms = 0.f;
+  if (e == hipSuccess) e = hipMemsetAsync(ctx->d_counters + 5, 0, sizeof(int), ctx->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
+  if (e == hipSuccess)
+    e = nr::launch_netbuild(ctx->d_data, n_samples, n_nodes, ctx->d_pairs, net_type, beta, ctx->d_counters + 5,
+                            ctx->stream);
+  if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(&bad, ctx->d_counters + 5, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+  for (hipEvent_t x : ev)
+    if (x) (void)hipEventDestroy(x);
+  if (e != hipSuccess) return hip_fail(ctx, e, "from-data build");
+  ctx->netbuild_ms = (double)ms;
+  ctx->symmetric = 1;  // every tile is stored and mirrored from the same bits
+  ctx->corr_finite = (bad & 2) ? 0 : 1;
+  ctx->net_finite = (bad & 4) ? 0 : 1;
+  ctx->n_nodes = n_nodes;
+  ctx->n_samples = n_samples;
+  return NR_OK;
+}
+}  // namespace
+
+int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples, int where,
+                             int flags, int net_type, double beta) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (flags & ~NR_SCALE_DATA) return fail(ctx, NR_ERR_INVALID, "unknown nr_set_dataset_from_data flags");
+  if (!data) return fail(ctx, NR_ERR_INVALID, "data missing");
+  if (n_nodes < 1 || n_samples < 2) return fail(ctx, NR_ERR_INVALID, "data needs n_nodes >= 1 and n_samples >= 2");
+  if (where != NR_HOST && where != NR_DEVICE) return fail(ctx, NR_ERR_INVALID, "where must be NR_HOST or NR_DEVICE");
+  if (net_type != NR_NET_UNSIGNED && net_type != NR_NET_SIGNED && net_type != NR_NET_SIGNED_HYBRID)
+    return fail(ctx, NR_ERR_INVALID, "unknown network type");
+  if (!std::isfinite(beta) || beta <= 0.0) return fail(ctx, NR_ERR_INVALID, "beta must be finite and > 0");
+  if (n_nodes > (int64_t)INT32_MAX) return fail(ctx, NR_ERR_UNSUPPORTED, "n_nodes exceeds 2^31-1");
+  NR_HIP(ctx, hipSetDevice(ctx->device));
+  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  reset_dataset(ctx);
+  const int rc = set_dataset_from_data_impl(ctx, data, n_nodes, n_samples, where, flags, net_type, beta);
+  if (rc != NR_OK) {
+    (void)hipStreamSynchronize(ctx->stream);
+    reset_dataset(ctx);
+  }
+  return rc;
+}
+
+int nr_netbuild_ms(nr_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return NR_ERR_INVALID;
+  *ms = ctx->d_pairs ? ctx->netbuild_ms : 0.0;
+  return NR_OK;
+}
+
+int nr_get_dataset_matrices(nr_ctx* ctx, double* corr_out, double* net_out) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (!ctx->d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
+  if (!corr_out && !net_out) return NR_OK;
+  NR_HIP(ctx, hipSetDevice(ctx->device));
+  // the table build replaces d_pairs between launches only; wait for both lanes
+  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->obs_stream) NR_HIP(ctx, hipStreamSynchronize(ctx->obs_stream));
+  const int64_t n_elem = ctx->n_nodes * ctx->n_nodes;
+  const int64_t chunk = std::min<int64_t>(n_elem, (int64_t)1 << 22);  // 32 MiB per matrix per chunk
+  const int parts = (corr_out ? 1 : 0) + (net_out ? 1 : 0);
+  double* d = nullptr;
+  NR_HIP(ctx, hipMalloc((void**)&d, (size_t)(parts * chunk) * sizeof(double)));
+  double* dc = corr_out ? d : nullptr;
+  double* dn = net_out ? d + (corr_out ? chunk : 0) : nullptr;
+  hipError_t e = hipSuccess;
+  for (int64_t o = 0; o < n_elem && e == hipSuccess; o += chunk) {
+    const int64_t len = std::min(chunk, n_elem - o);
+    e = nr::launch_deinterleave(ctx->d_pairs, ctx->pairs_es, o, len, dc, dn, ctx->stream);
+    if (e == hipSuccess && dc)
+      e = hipMemcpyAsync(corr_out + o, dc, (size_t)len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess && dn)
+      e = hipMemcpyAsync(net_out + o, dn, (size_t)len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the staging buffer is free again
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess) return hip_fail(ctx, e, "matrix export");
+  return NR_OK;
+}
 
 // File -> pinned -> HBM for one matrix payload: the host inflates / reads
 // straight into pinned buffer b while the copy engine moves the previous one

@@ -738,6 +738,103 @@ int netrep_PermutationProcedureFiles(const netrep_disc_props* disc, const char* 
   return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
 }
 
+}  // extern "C"
+
+namespace {
+
+// The argument checks of the from-data entries (before any context is opened).
+int check_from_data_args(const double* data, int32_t net_type, double beta, int64_t n_samples, int64_t n_nodes) {
+  if (!data) return set_err(NR_ERR_INVALID, "data missing");
+  if (n_samples < 2 || n_nodes < 1) return set_err(NR_ERR_INVALID, "data needs n_samples >= 2 and n_nodes >= 1");
+  if (net_type != NR_NET_UNSIGNED && net_type != NR_NET_SIGNED && net_type != NR_NET_SIGNED_HYBRID)
+    return set_err(NR_ERR_INVALID, "unknown network type");
+  if (!std::isfinite(beta) || beta <= 0.0) return set_err(NR_ERR_INVALID, "beta must be finite and > 0");
+  return NR_OK;
+}
+
+// Context 0 with the dataset built from `data`; on failure the context goes
+// back to the pool.
+int open_from_data(const double* data, int32_t scale_data, int32_t net_type, double beta, int64_t n_samples,
+                   int64_t n_nodes, int32_t n_cores, CtxPtr& ctx) {
+  int rc = open_ctx(0, ctx);
+  if (rc) return rc;
+  if (n_cores != 0) nr_ctx_set_host_threads(ctx.get(), n_cores);
+  rc = nr_set_dataset_from_data(ctx.get(), data, n_nodes, n_samples, NR_HOST, scale_data ? NR_SCALE_DATA : 0,
+                                net_type, beta);
+  if (rc) {
+    rc = ctx_err(rc, ctx.get());
+    give_ctx(ctx);
+  }
+  return rc;
+}
+
+int from_data_once(const netrep_disc_props* disc, const double* t_data, int32_t scale_data, int32_t net_type,
+                   double beta, int64_t n_samples, int64_t n_nodes, const char* const* t_names,
+                   const char* const* ma_names, const char* const* ma_labels, int64_t n_assign,
+                   const char* const* modules, int64_t n_modules, int64_t n_perm, int32_t n_cores,
+                   const char* null_hypothesis, int32_t verbose, uint64_t seed, const uint32_t* pi,
+                   double* nulls_out, double* observed_out) {
+  CtxPtr ctx;
+  int rc = open_from_data(t_data, scale_data, net_type, beta, n_samples, n_nodes, n_cores, ctx);
+  if (rc) return rc;
+  int cf = 0, nf = 0;
+  nr_dataset_finite(ctx.get(), &cf, &nf);
+  if (!cf || !nf) {  // R/check-user-input.R:796-799, before any permutation runs
+    give_ctx(ctx);
+    return set_err(NR_ERR_NONFINITE, "matrices cannot have non-finite or missing values");
+  }
+  return permutation_impl(disc, true, nullptr, nullptr, nullptr, n_samples, n_nodes, t_names, ma_names, ma_labels,
+                          n_assign, modules, n_modules, n_perm, null_hypothesis, verbose, seed, pi, nulls_out,
+                          observed_out, std::move(ctx), n_cores);
+}
+
+}  // namespace
+
+extern "C" {
+
+int netrep_PermutationProcedureFromData(const netrep_disc_props* disc, const double* t_data, int32_t scale_data,
+                                        int32_t net_type, double beta, int64_t n_samples, int64_t n_nodes,
+                                        const char* const* t_names, const char* const* ma_names,
+                                        const char* const* ma_labels, int64_t n_assign, const char* const* modules,
+                                        int64_t n_modules, int64_t n_perm, int32_t n_cores,
+                                        const char* null_hypothesis, int32_t verbose, uint64_t seed,
+                                        const uint32_t* pi, double* nulls_out, double* observed_out) try {
+  if (int rc = check_from_data_args(t_data, net_type, beta, n_samples, n_nodes)) return rc;
+  if (!disc || !t_names || !ma_names || !ma_labels || !modules || !observed_out || n_perm < 0 ||
+      (n_perm > 0 && !nulls_out))
+    return set_err(NR_ERR_INVALID, "invalid arguments to PermutationProcedureFromData");
+  int rc = from_data_once(disc, t_data, scale_data, net_type, beta, n_samples, n_nodes, t_names, ma_names, ma_labels,
+                          n_assign, modules, n_modules, n_perm, n_cores, null_hypothesis, verbose, seed, pi,
+                          nulls_out, observed_out);
+  if (rc == NR_ERR_OOM) {  // as netrep_PermutationProcedure: free what is held between calls, once
+    netrep_ReleaseResident();
+    rc = from_data_once(disc, t_data, scale_data, net_type, beta, n_samples, n_nodes, t_names, ma_names, ma_labels,
+                        n_assign, modules, n_modules, n_perm, n_cores, null_hypothesis, verbose, seed, pi,
+                        nulls_out, observed_out);
+  }
+  return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_BuildNetwork(const double* data, int32_t scale_data, int32_t net_type, double beta, int64_t n_samples,
+                        int64_t n_nodes, double* corr_out, double* net_out) try {
+  if (int rc = check_from_data_args(data, net_type, beta, n_samples, n_nodes)) return rc;
+  CtxPtr ctx;
+  int rc = open_from_data(data, scale_data, net_type, beta, n_samples, n_nodes, 0, ctx);
+  if (rc) return rc;
+  rc = nr_get_dataset_matrices(ctx.get(), corr_out, net_out);
+  if (rc) rc = ctx_err(rc, ctx.get());
+  give_ctx(ctx);
+  return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
 int netrep_ReadRDSMatrix(const char* path, const char* object, int64_t* nrow, int64_t* ncol, double* out,
                          char* colnames, int64_t colnames_cap, int64_t* colnames_needed) try {
   if (!path || !nrow || !ncol) return set_err(NR_ERR_INVALID, "invalid arguments to ReadRDSMatrix");

@@ -209,6 +209,19 @@ hipError_t launch_profile(const ProfileParams& P, int n_slots, int variant, int 
 hipError_t launch_interleave(const double* corr, const double* net, double2* out, int64_t n_elem,
                              hipStream_t st);
 hipError_t launch_symmetry(const double2* a, int64_t n, int* asym, hipStream_t st);
+// The from-data path (netbuild.hip): {corr, net} pairs (es = 1) of the scaled
+// block X (S x (n + 2), the virtual columns behind): corr = clamp(x_i . x_j /
+// (S - 1), -1, 1), net by net_type (NR_NET_*) and beta, one workgroup per
+// kNetbuildTile-square tile of the lower triangle, each tile stored at (i, j)
+// and mirrored at (j, i). flags (symmetry_kernel's layout): |= 2 for a
+// non-finite corr, |= 4 for a non-finite net.
+constexpr int kNetbuildTile = 64;
+hipError_t launch_netbuild(const double* X, int64_t S, int64_t n, double2* pairs, int net_type, double beta,
+                           int* flags, hipStream_t st);
+// corr[e], net[e] (either may be NULL) = elements [first, first + len) of a
+// pair array in layout es (1, or 2: the Gram table).
+hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,
+                               hipStream_t st);
 hipError_t launch_scale(const double* in, double* out, int64_t S, int64_t N, hipStream_t st);
 // XDR (big-endian) doubles -> native: into pairs[i].x (half 0) / .y (half 1), or `plain`
 hipError_t launch_xdr(const void* raw, double2* pairs, int half, double* plain, int64_t n, hipStream_t st);

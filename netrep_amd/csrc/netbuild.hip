@@ -1,0 +1,280 @@
+// The from-data path (nr_set_dataset_from_data): the resident {corr, net} pair
+// array computed on the device from the scaled data block, as the reference's
+// example data derives it on the host (R/example-data.R:111-116: cor(data),
+// abs(correlation)^5), and the export of a resident pair array back to two
+// plain matrices (nr_get_dataset_matrices).
+//
+// netbuild_kernel: a lower-triangle SYRK on v_mfma_f64_16x16x4_f64. One
+// 256-thread workgroup owns one kNetbuildTile x kNetbuildTile (64 x 64) tile
+// (I, J), I >= J, of g = X^T X; its four waves own one 32 x 32 quadrant each
+// (2 x 2 MFMA tiles). The two 64-column panels go through LDS in chunks of
+// kNbChunk samples: every operand element is fetched from global memory once
+// per workgroup tile, and the next chunk's loads are in flight while the
+// current one is multiplied. The epilogue turns g into {c, w} per element and
+// stores the tile twice, at (i, j) and -- the same bits -- at (j, i). Both
+// stores go through an LDS image of half the tile so that each wave
+// instruction writes 16 bytes per lane along contiguous rows of the
+// column-major array: neither store is strided by n.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/netrep_gpu.h"
+#include "kernels.h"
+
+namespace nr {
+
+namespace {
+
+typedef double nb_f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kNbTile = kNetbuildTile;  // 64: output tile side per workgroup
+constexpr int kNbChunk = 32;            // samples per LDS chunk (8 MFMA K-steps)
+// Doubles per panel column in LDS: kNbChunk + 2. A lane reads 16 bytes at
+// column * 272 + const, so 8 consecutive lanes (the group one ds_read_b128
+// cycle serves) fall on banks 0, 4, ..., 28 (+ const): conflict-free.
+constexpr int kNbLd = kNbChunk + 2;
+// The epilogue's LDS images of half a tile (32 columns j x 64 rows i): g as
+// doubles, then {c, w} as double2, both with 65 elements per column (130 / 260
+// dwords = 2 / 4 mod 64): conflict-free for the 8-byte writes of the MFMA
+// layout and for the 16-byte accesses along either direction.
+constexpr int kNbOutLd = kNbTile + 1;
+constexpr int kNbPanelDoubles = 2 * kNbTile * kNbLd;       // 4,352 doubles = 34,816 bytes
+constexpr int kNbHalfG = (kNbTile / 2) * kNbOutLd;         // 2,080 doubles
+constexpr int kNbStageDoubles = kNbHalfG + 2 * kNbHalfG;   // 6,240 doubles = 49,920 bytes
+constexpr int kNbLdsDoubles = kNbPanelDoubles > kNbStageDoubles ? kNbPanelDoubles : kNbStageDoubles;
+
+// The lower-triangle tile (I, J), I >= J, of linear index t = I (I + 1) / 2 + J.
+__device__ __forceinline__ void tile_of(int64_t t, int64_t& I, int64_t& J) {
+  int64_t i = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+  while (i * (i + 1) / 2 > t) --i;
+  while ((i + 1) * (i + 2) / 2 <= t) ++i;
+  I = i;
+  J = t - i * (i + 1) / 2;
+}
+
+// c -> w of the three network types through one pow; NaN in, NaN out (the
+// hybrid's test is written so that it is false for NaN).
+__device__ __forceinline__ double net_weight(double c, int net_type, double beta) {
+  const double base = net_type == NR_NET_UNSIGNED ? fabs(c) : (net_type == NR_NET_SIGNED ? (1.0 + c) * 0.5 : c);
+  const double w = pow(base, beta);
+  return net_type == NR_NET_SIGNED_HYBRID && c <= 0.0 ? 0.0 : w;
+}
+
+// One chunk of a thread's share of both panels: 4 + 4 double2, rows
+// [s0 + 2 (t & 15), + 2) of columns (t >> 4) + 16 p of panel A (tile I) and B
+// (tile J). Columns past n read the block's zero column. Branch-free, so that
+// the eight loads are in flight together: a whole chunk (FULL) loads 16 bytes
+// per column; the last, partial chunk loads each row from an address clamped
+// into the column and zeroes the rows past S afterwards.
+struct NbFetch {
+  double2 a[4], b[4];
+};
+
+template <bool FULL>
+__device__ __forceinline__ void nb_fetch(const double* __restrict__ X, int64_t S, const int64_t (&col_a)[4],
+                                         const int64_t (&col_b)[4], int64_t s0, NbFetch& f) {
+  const int64_t r = s0 + 2 * (threadIdx.x & 15);
+  if (FULL) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {  // columns start at any multiple of 8 bytes (S odd): memcpy, not a double2 load
+      __builtin_memcpy(&f.a[p], X + col_a[p] + r, sizeof(double2));
+      __builtin_memcpy(&f.b[p], X + col_b[p] + r, sizeof(double2));
+    }
+  } else {
+    const int64_t r0 = r < S ? r : S - 1, r1 = r + 1 < S ? r + 1 : S - 1;
+    const double m0 = r < S ? 1.0 : 0.0, m1 = r + 1 < S ? 1.0 : 0.0;
+    double t[4][4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      t[p][0] = X[col_a[p] + r0];
+      t[p][1] = X[col_a[p] + r1];
+      t[p][2] = X[col_b[p] + r0];
+      t[p][3] = X[col_b[p] + r1];
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {  // selects, not products: a NaN or Inf above the clamp must not leak
+      f.a[p] = make_double2(m0 != 0.0 ? t[p][0] : 0.0, m1 != 0.0 ? t[p][1] : 0.0);
+      f.b[p] = make_double2(m0 != 0.0 ? t[p][2] : 0.0, m1 != 0.0 ? t[p][3] : 0.0);
+    }
+  }
+}
+
+// This thread's share of a chunk into the panels.
+__device__ __forceinline__ void nb_to_lds(double* pA, double* pB, const NbFetch& f) {
+  const int kp = 2 * (threadIdx.x & 15), c0 = threadIdx.x >> 4;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    *reinterpret_cast<double2*>(pA + (c0 + 16 * p) * kNbLd + kp) = f.a[p];
+    *reinterpret_cast<double2*>(pB + (c0 + 16 * p) * kNbLd + kp) = f.b[p];
+  }
+}
+
+// The wave's 2 x 2 MFMA tiles over one chunk in LDS: lane (i16, kk) feeds rows
+// 8 kk .. 8 kk + 7 of the chunk, one per MFMA (the same rows on both operands;
+// which row goes with which K-step only permutes the sum).
+__device__ __forceinline__ void nb_multiply(const double* pA, const double* pB, int wr, int wc, int i16, int kk,
+                                            nb_f64x4 (&acc)[2][2]) {
+  double va[2][8], vb[2][8];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    const double* ra = pA + (32 * wr + 16 * a + i16) * kNbLd + 8 * kk;
+    const double* rb = pB + (32 * wc + 16 * a + i16) * kNbLd + 8 * kk;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double2 x = *reinterpret_cast<const double2*>(ra + 2 * q);
+      const double2 y = *reinterpret_cast<const double2*>(rb + 2 * q);
+      va[a][2 * q] = x.x;
+      va[a][2 * q + 1] = x.y;
+      vb[a][2 * q] = y.x;
+      vb[a][2 * q + 1] = y.y;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[0][q], vb[0][q], acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[0][q], vb[1][q], acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[1][q], vb[0][q], acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(va[1][q], vb[1][q], acc[1][1], 0, 0, 0);
+  }
+}
+
+__global__ void __launch_bounds__(256, 2)
+netbuild_kernel(const double* __restrict__ X, int64_t S, int64_t n, double2* __restrict__ pairs, int net_type,
+                double beta, int* __restrict__ flags) {
+  __shared__ __attribute__((aligned(16))) double lds[kNbLdsDoubles];
+  double* const pA = lds;                       // [64 columns][kNbLd]
+  double* const pB = lds + kNbTile * kNbLd;
+  double* const stage_g = lds;                                          // [32 columns j][kNbOutLd rows i]
+  double2* const stage = reinterpret_cast<double2*>(lds + kNbHalfG);    // the same shape, {c, w}
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i16 = lane & 15, kk = lane >> 4;
+  const int wr = wave & 1, wc = wave >> 1;  // the wave's quadrant: rows 32 wr.., columns 32 wc..
+  const int64_t nT = (n + kNbTile - 1) / kNbTile;
+  const int64_t n_tiles = nT * (nT + 1) / 2;
+  const int64_t zero_col = (n + 1) * S;
+  const double denom = (double)(S - 1);
+  int bad = 0;
+
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    int64_t I, J;
+    tile_of(t, I, J);
+    const bool diag = I == J;
+
+    nb_f64x4 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) acc[a][b] = nb_f64x4{0.0, 0.0, 0.0, 0.0};
+
+    int64_t col_a[4], col_b[4];  // offsets of this thread's panel columns in X
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int64_t ca = I * kNbTile + (threadIdx.x >> 4) + 16 * p, cb = J * kNbTile + (threadIdx.x >> 4) + 16 * p;
+      col_a[p] = ca < n ? ca * S : zero_col;
+      col_b[p] = cb < n ? cb * S : zero_col;
+    }
+    // whole chunks: the next chunk's loads are in flight while this one is
+    // multiplied; the last, partial chunk (its own code, so that its waits
+    // never sit in the whole chunks' path) after them
+    const int64_t s_full = S / kNbChunk * kNbChunk;
+    NbFetch f;
+    if (s_full > 0) nb_fetch<true>(X, S, col_a, col_b, 0, f);
+    for (int64_t s0 = 0; s0 < s_full; s0 += kNbChunk) {
+      nb_to_lds(pA, pB, f);
+      __syncthreads();
+      if (s0 + kNbChunk < s_full) nb_fetch<true>(X, S, col_a, col_b, s0 + kNbChunk, f);
+      nb_multiply(pA, pB, wr, wc, i16, kk, acc);
+      __syncthreads();  // the panels are free (for the next chunk, or the output image)
+    }
+    if (s_full < S) {
+      nb_fetch<false>(X, S, col_a, col_b, s_full, f);
+      nb_to_lds(pA, pB, f);
+      __syncthreads();
+      nb_multiply(pA, pB, wr, wc, i16, kk, acc);
+      __syncthreads();
+    }
+
+    // Epilogue, one half of the tile's columns (held by the waves wc == h) at
+    // a time: g into stage_g[j][i]; every thread turns 8 elements into {c, w}
+    // in stage[j][i]; then out along i (the (i, j) store) and along j (the
+    // mirror at (j, i)).
+    for (int h = 0; h < 2; ++h) {
+      if (wc == h) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              // D[row = (lane >> 4) + 4 r][col = lane & 15] (f64 MFMA C/D map)
+              stage_g[(16 * b + i16) * kNbOutLd + 32 * wr + 16 * a + kk + 4 * r] = acc[a][b][r];
+      }
+      __syncthreads();
+#pragma unroll 1
+      for (int q = 0; q < 8; ++q) {
+        const int il = lane, jl = wave + 4 * q;
+        const int64_t gi = I * kNbTile + il, gj = J * kNbTile + 32 * h + jl;
+        double c = stage_g[jl * kNbOutLd + il] / denom;
+        c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);  // R's cor clamps; NaN stays NaN
+        const double w = net_weight(c, net_type, beta);
+        if (gi < n && gj < n && (!diag || gi >= gj)) bad |= (isfinite(c) ? 0 : 2) | (isfinite(w) ? 0 : 4);
+        stage[jl * kNbOutLd + il] = make_double2(c, w);
+      }
+      __syncthreads();
+      // (i, j): one column of 64 rows per wave instruction (1 KiB contiguous)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int jl = 8 * wave + q;
+        const int64_t gi = I * kNbTile + lane, gj = J * kNbTile + 32 * h + jl;
+        if (gi < n && gj < n && (!diag || gi >= gj)) pairs[gi + gj * n] = stage[jl * kNbOutLd + lane];
+      }
+      // (j, i): two rows i of 32 columns j per wave instruction (2 x 512 contiguous bytes)
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int il = 16 * wave + 2 * q + (lane >> 5), jl = lane & 31;
+        const int64_t gi = I * kNbTile + il, gj = J * kNbTile + 32 * h + jl;
+        if (gi < n && gj < n && (!diag || gi >= gj)) pairs[gj + gi * n] = stage[jl * kNbOutLd + il];
+      }
+      __syncthreads();
+    }
+  }
+  // one reduction per wave, one atomic per wave that saw a non-finite value
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad |= __shfl_xor(bad, o, 64);
+  if (bad && lane == 0) atomicOr(flags, bad);
+}
+
+// corr[e] / net[e] of elements [first, first + len) of a pair array with
+// element stride es (1: {corr, net}; 2: the Gram-table layout).
+__global__ void deinterleave_kernel(const double2* __restrict__ pairs, int es, int64_t first, int64_t len,
+                                    double* __restrict__ corr, double* __restrict__ net) {
+  for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < len; e += (int64_t)gridDim.x * blockDim.x) {
+    const double2 p = pairs[(first + e) * es];
+    if (corr) corr[e] = p.x;
+    if (net) net[e] = p.y;
+  }
+}
+
+}  // namespace
+
+hipError_t launch_netbuild(const double* X, int64_t S, int64_t n, double2* pairs, int net_type, double beta,
+                           int* flags, hipStream_t st) {
+  const int64_t nT = (n + kNbTile - 1) / kNbTile;
+  const int64_t n_tiles = nT * (nT + 1) / 2;
+  const unsigned g = (unsigned)std::min<int64_t>(n_tiles, (int64_t)1 << 20);
+  hipLaunchKernelGGL(netbuild_kernel, dim3(g), dim3(256), 0, st, X, S, n, pairs, net_type, beta, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,
+                               hipStream_t st) {
+  if (len <= 0) return hipSuccess;
+  const unsigned g = (unsigned)std::min<int64_t>((len + 255) / 256, 8192);
+  hipLaunchKernelGGL(deinterleave_kernel, dim3(g), dim3(256), 0, st, pairs, es, first, len, corr, net);
+  return hipGetLastError();
+}
+
+}  // namespace nr

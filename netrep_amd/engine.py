@@ -34,6 +34,9 @@ STAMP_SLOTS = ["index", "gram", "lanczos_setup", "matvec", "three_term_omega", "
 class Engine:
     """One GPU context. ``device`` is the HIP ordinal."""
 
+    # side of the from-data kernel's workgroup tile (kNetbuildTile, csrc/kernels.h)
+    NETBUILD_TILE = 64
+
     def __init__(self, device: int = 0):
         self._lib = L.load()
         h = C.c_void_p()
@@ -86,6 +89,38 @@ class Engine:
         self.n_stat = 7 if data is not None else 4
         self.n_nodes = n
         self.n_samples = s
+
+    def set_dataset_from_data(self, data, beta, net_type="unsigned", scale=True):
+        """The resident dataset from the data matrix alone (S x N, host numpy):
+        only `data` is uploaded (scaled on the device unless ``scale=False``:
+        already scaled); corr = cor(data) and net (``net_type`` 'unsigned'
+        |corr|^beta, 'signed' ((1 + corr) / 2)^beta, 'signed_hybrid' corr^beta
+        for corr > 0, else 0) are built in HBM (nr_set_dataset_from_data)."""
+        d = _f64(data)
+        if d.ndim != 2:
+            raise ValueError("data must be a samples x nodes matrix")
+        s, n = d.shape
+        self._check(self._lib.nr_set_dataset_from_data(self._h, _ptr(d), n, s, L.NR_HOST,
+                                                       L.NR_SCALE_DATA if scale else 0,
+                                                       L.net_type_code(net_type), float(beta)))
+        self.n_stat = 7
+        self.n_nodes = n
+        self.n_samples = s
+
+    def matrices(self):
+        """(corr, net) of the resident dataset as host arrays (nr_get_dataset_matrices)."""
+        n, _s = self.shape()
+        corr = np.empty((n, n), dtype=np.float64, order="F")
+        net = np.empty((n, n), dtype=np.float64, order="F")
+        self._check(self._lib.nr_get_dataset_matrices(self._h, _ptr(corr), _ptr(net)))
+        return corr, net
+
+    def netbuild_ms(self) -> float:
+        """Device time in ms of the from-data build of the resident matrices
+        (nr_netbuild_ms), 0 for a dataset made any other way."""
+        ms = C.c_double()
+        self._check(self._lib.nr_netbuild_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def set_dataset_files(self, corr_path, net_path, data_path=None, objects=(None, None, None),
                           scale_data=True):
