@@ -94,7 +94,8 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
                              int where, int flags, int net_type, double beta);
 /* Device time in ms (HIP events on the context's stream) of the kernel that
  * built the resident dataset's matrices from its data; 0 for a dataset made
- * any other way. */
+ * any other way. A copy (nr_copy_dataset, nr_broadcast_dataset) reports the
+ * figure of the dataset it was copied from. */
 int nr_netbuild_ms(nr_ctx* ctx, double* ms);
 /* The resident corr and net (n_nodes x n_nodes each, column-major) to host
  * arrays; either may be NULL. Works for a dataset made by any of the

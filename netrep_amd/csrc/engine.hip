@@ -1,5 +1,6 @@
-// Engine layer of the C ABI (include/netrep_gpu.h): per-GPU context, dataset
-// residency in HBM, batched permutation launches, progress and cancellation.
+// Engine layer of the C ABI (include/netrep_gpu.h): per-GPU context, batched
+// permutation launches, progress and cancellation (dataset residency in HBM:
+// dataset.hip).
 //
 // Replaces PermutationProcedure's thread pool (src/permutations.cpp:334-380):
 // instead of nThreads contiguous chunks of permutations walked one module at a
@@ -18,169 +19,18 @@
 #include <mutex>
 #include <thread>
 #include <string>
-#include <set>
 #include <vector>
 
-#include "../../include/netrep_gpu.h"
+#include "engine_internal.h"
 #include "kernels.h"
 #include "prp.h"
-#include "rds_reader.h"
 
 namespace {
 
 thread_local std::string g_create_error;
 
-// Host -> device bytes moved by the library since it was loaded (nr_h2d_bytes):
-// every upload path adds what it copies, so a caller can check that a
-// resident dataset is not uploaded again.
-std::atomic<int64_t> g_h2d_bytes{0};
-
 // Default host threads of the staging copies for new contexts (nr_set_host_threads).
 std::atomic<int> g_host_threads{8};
-
-struct DeviceTimer {
-  double ms = 0.0;
-  int64_t launches = 0;
-  int64_t items = 0;
-};
-
-}  // namespace
-
-struct nr_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  std::mutex mu;
-  int host_threads = 8;  // host threads of this context's staging copies (nr_ctx_set_host_threads)
-
-  // resident dataset
-  double2* d_pairs = nullptr;
-  int32_t pairs_es = 1;          // d_pairs element stride in double2: 2 = the Gram table layout,
-                                 // 0 = the packed lower triangle (symmetric matrices; pack rule below)
-  double* d_colsum = nullptr;    // [n_nodes] column sums of the data (Gram table)
-  int64_t table_checked = -1;    // modules_serial the Gram-table decision was made for
-  double table_ms = 0.0;         // wall time of the last Gram-table build
-  double netbuild_ms = 0.0;      // device time of the from-data build of the matrices (0: not built from data)
-  double* d_data = nullptr;
-  int64_t n_nodes = 0, n_samples = 0;
-  std::vector<std::string> node_names;  // column names of a dataset loaded from files
-  int64_t data_gen = 0;                 // bumped by every dataset change (reset_dataset)
-  int64_t modules_gen = -1;             // data_gen the modules were validated against
-  int64_t modules_serial = 0;           // bumped by every nr_set_modules
-  int64_t null_gen = -1;                // data_gen the null pool was validated against
-  int symmetric = 0;
-  int corr_finite = 0, net_finite = 0;  // CheckFinite of the resident matrices
-  int disc_cv_finite = 0;               // the present modules' discovery CorrVector is all finite
-
-  // modules
-  int32_t n_rows = 0, n_present = 0, k_max = 0;
-  int64_t n_node_total = 0, n_cv_total = 0;
-  int64_t null_pos_max = -1;  // largest null-pool position of any module node (-1: none)
-  std::vector<int64_t> node_off_h, cv_off_h;
-  int32_t* d_row_of = nullptr;
-  int64_t* d_node_off = nullptr;
-  int64_t* d_cv_off = nullptr;
-  int32_t* d_test_idx = nullptr;
-  int32_t* d_null_pos = nullptr;
-  double* d_disc_cv = nullptr;
-  double* d_disc_wd = nullptr;
-  double* d_disc_nc = nullptr;
-  double* d_cv_shift = nullptr;
-  int32_t* d_mod_order = nullptr;
-  std::vector<int32_t> order_k_h;  // module sizes in d_mod_order's order (descending)
-
-  // null pool
-  int32_t* d_null_idx = nullptr;
-  int64_t n_null = 0;
-
-  // run buffers
-  double* d_out = nullptr;
-  size_t out_cap = 0;
-  double* h_stage = nullptr;
-  size_t stage_cap = 0;
-  uint32_t* d_pi = nullptr;
-  size_t pi_cap = 0;
-  double* d_scratch = nullptr;
-  size_t scratch_cap = 0;
-  double* d_net_scratch = nullptr;  // per-workgroup node arrays of modules too large for LDS
-  size_t net_scratch_cap = 0;
-  int* d_counters = nullptr;  // [0] queue head, [1..4] lanczos diagnostics, [5] flag
-  int64_t batch = 0;          // 0 = automatic
-  // the second output / staging buffer of run_impl's two batches in flight
-  double* d_out2 = nullptr;
-  size_t out2_cap = 0;
-  double* h_stage2 = nullptr;
-  size_t stage2_cap = 0;
-  double* h_scale = nullptr;  // nr_scale's pinned staging (4 column chunks)
-  size_t scale_cap = 0;
-  double* d_scale = nullptr;  // and its device chunks (kept between calls, released as scratch)
-  size_t d_scale_cap = 0;
-  hipEvent_t ev_copy[2] = {nullptr, nullptr};
-
-  // The observed statistics' own lane (nr_observed_async): stream, scratch and
-  // work queue, so that they run beside the first permutation batch instead
-  // of ahead of it (at C5 the one-item-per-module launch held the GPU ~85 ms
-  // per PermutationProcedure call with 40 workgroups busy).
-  hipStream_t obs_stream = nullptr;
-  double* obs_scratch = nullptr;
-  size_t obs_scratch_cap = 0;
-  double* obs_net_scratch = nullptr;
-  size_t obs_net_cap = 0;
-  int* obs_counters = nullptr;
-  double* d_obs = nullptr;
-  size_t obs_cap = 0;
-  bool obs_pending = false;  // cleared by every change of dataset, modules or null pool
-
-  // the column sweep's per-batch work buffers (sweep.hip), one set per lane
-  struct SweepBuf {
-    int32_t *col = nullptr, *rank = nullptr, *lrank = nullptr, *count = nullptr, *col_off = nullptr;
-    uint32_t *sorted = nullptr, *bndh = nullptr;
-    uint4* meta = nullptr;
-    double *rec = nullptr, *dabs = nullptr;
-    double* zs = nullptr;  // [4] zeros + [256] sink (sweep.hip: lanes with nothing to load / store)
-    size_t occ_cap = 0, col_cap = 0;
-    int32_t chunk_cap = 0;
-  } sweep[2];
-
-  std::atomic<int64_t> done{0}, total{0};
-  std::atomic<bool> cancel{false};
-
-  bool timing = false;
-  unsigned long long* d_stamps = nullptr;  // phase stamps (nr_set_stamps)
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  bool ev_pending[2] = {false, false};
-  DeviceTimer timers[2];
-};
-
-namespace {
-
-int fail(nr_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  return code;
-}
-
-int hip_fail(nr_ctx* ctx, hipError_t e, const char* what) {
-  return fail(ctx, e == hipErrorOutOfMemory ? NR_ERR_OOM : NR_ERR_HIP,
-              std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define NR_HIP(ctx, call)                              \
-  do {                                                 \
-    hipError_t e_ = (call);                            \
-    if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); \
-  } while (0)
-
-template <typename T>
-void dfree(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
-
-// Every host -> device copy of the library goes through here (counted).
-hipError_t h2d_async(void* dst, const void* src, size_t bytes, hipStream_t st) {
-  g_h2d_bytes.fetch_add((int64_t)bytes);
-  return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
-}
 
 template <typename T>
 int upload(nr_ctx* ctx, T*& dst, const T* src, size_t n) {
@@ -191,44 +41,11 @@ int upload(nr_ctx* ctx, T*& dst, const T* src, size_t n) {
   return NR_OK;
 }
 
-template <typename T>
-int ensure(nr_ctx* ctx, T*& buf, size_t& cap, size_t n) {
-  if (n <= cap && buf) return NR_OK;
-  dfree(buf);
-  NR_HIP(ctx, hipMalloc((void**)&buf, n * sizeof(T)));
-  cap = n;
-  return NR_OK;
-}
-
-int ensure_stage(nr_ctx* ctx, double*& h, size_t& cap, size_t n) {
-  if (n <= cap && h) return NR_OK;
-  if (h) (void)hipHostFree(h);
-  h = nullptr;
-  NR_HIP(ctx, hipHostMalloc((void**)&h, n * sizeof(double), hipHostMallocDefault));
-  cap = n;
-  return NR_OK;
-}
-
 __global__ void na_fill_kernel(double* p, int64_t n) {
   const double na = __longlong_as_double(0x7FF00000000007A2ll);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x)
     p[i] = na;
-}
-
-__global__ void fill_kernel(double* p, int64_t n, double v) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    p[i] = v;
-}
-
-// The Gram's virtual columns behind the resident data block: column N all
-// ones, column N + 1 zeros (ProfileParams::ones_off).
-int fill_virtual_columns(nr_ctx* ctx, int64_t n_nodes, int64_t n_samples) {
-  double* ones = ctx->d_data + n_nodes * n_samples;
-  hipLaunchKernelGGL(fill_kernel, dim3(64), dim3(256), 0, ctx->stream, ones, n_samples, 1.0);
-  NR_HIP(ctx, hipGetLastError());
-  NR_HIP(ctx, hipMemsetAsync(ones + n_samples, 0, (size_t)n_samples * sizeof(double), ctx->stream));
-  return NR_OK;
 }
 
 int fill_na(nr_ctx* ctx, double* d, int64_t n, hipStream_t st = nullptr) {
@@ -239,40 +56,7 @@ int fill_na(nr_ctx* ctx, double* d, int64_t n, hipStream_t st = nullptr) {
   return NR_OK;
 }
 
-int n_stat_of(const nr_ctx* ctx) { return ctx->d_data ? NR_NSTAT_DATA : NR_NSTAT_NODATA; }
-
-// Bytes of the resident {corr, net} array in its layout (pairs_es).
-size_t pair_bytes_of(const nr_ctx* ctx) {
-  const size_t n = (size_t)ctx->n_nodes;
-  return n * n * sizeof(double2) * (size_t)ctx->pairs_es;
-}
-
-// No dataset: buffers freed, shape zero. Modules validated against an earlier
-// dataset (their node indices) stop being usable: check_ready demands a new
-// nr_set_modules after any dataset change.
-// Wait for an observed launch still running on the second lane (before its
-// inputs are replaced or freed) and drop its result: nr_observed_wait then
-// refuses until nr_observed_async is called again.
-void sync_obs(nr_ctx* ctx) {
-  if (ctx->obs_stream) (void)hipStreamSynchronize(ctx->obs_stream);
-  ctx->obs_pending = false;
-}
-
-void reset_dataset(nr_ctx* ctx) {
-  sync_obs(ctx);
-  dfree(ctx->d_pairs);
-  dfree(ctx->d_data);
-  dfree(ctx->d_colsum);
-  ctx->pairs_es = 1;
-  ctx->table_checked = -1;
-  ctx->netbuild_ms = 0.0;
-  ctx->node_names.clear();
-  ctx->n_nodes = 0;
-  ctx->n_samples = 0;
-  ctx->symmetric = 0;
-  ctx->corr_finite = ctx->net_finite = 0;
-  ++ctx->data_gen;
-}
+int n_stat_of(const nr_ctx* ctx) { return ctx->ds.d_data ? NR_NSTAT_DATA : NR_NSTAT_NODATA; }
 
 // Lanczos basis columns per item: 160 covers every C2/C3 module (<= 46 steps
 // measured); large modules (C5: up to 2,000 nodes, spectra with small gaps)
@@ -645,8 +429,8 @@ int launch_sweep_batch(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, con
   // occurrences per sub-batch: at most kSweepMaxOcc, and records of at most
   // kSweepMaxRecBytes (many column chunks at large n)
   const int64_t chunks =
-      (ctx->n_nodes + nr::sweep_chunk_rows(ctx->n_nodes, np.disc_cv ? 16 : 8) - 1) /
-      nr::sweep_chunk_rows(ctx->n_nodes, np.disc_cv ? 16 : 8);
+      (ctx->ds.n_nodes + nr::sweep_chunk_rows(ctx->ds.n_nodes, np.disc_cv ? 16 : 8) - 1) /
+      nr::sweep_chunk_rows(ctx->ds.n_nodes, np.disc_cv ? 16 : 8);
   const int64_t max_occ = std::min<int64_t>(g_sweep_max_occ.load(), kSweepMaxRecBytes / (chunks * 8 * nr::kSweepRec));
   const int64_t per = std::max<int64_t>(1, max_occ / std::max<int64_t>(ctx->n_node_total, 1));
   for (int64_t p0 = 0; p0 < n_perm; p0 += per) {
@@ -664,8 +448,8 @@ int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const
   nr_ctx::SweepBuf& b = ctx->sweep[ln.id];
   const size_t n_occ = (size_t)(n_perm * ctx->n_node_total);
   nr::SweepParams P{};
-  P.chunk_rows = nr::sweep_chunk_rows(ctx->n_nodes, np.disc_cv ? 16 : 8);
-  P.n_chunks = (int32_t)((ctx->n_nodes + P.chunk_rows - 1) / P.chunk_rows);
+  P.chunk_rows = nr::sweep_chunk_rows(ctx->ds.n_nodes, np.disc_cv ? 16 : 8);
+  P.n_chunks = (int32_t)((ctx->ds.n_nodes + P.chunk_rows - 1) / P.chunk_rows);
   // Every buffer of a set is freed before it is reallocated, so a set's
   // capacity is committed only once the whole chain has succeeded: after an
   // allocation failure the capacity reads 0 and the next call reallocates
@@ -693,7 +477,7 @@ int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const
     NR_HIP(ctx, hipMalloc((void**)&b.zs, (4 + 256) * sizeof(double)));
     NR_HIP(ctx, hipMemsetAsync(b.zs, 0, 4 * sizeof(double), ln.st));
   }
-  const size_t n_cols = (size_t)ctx->n_nodes + 1;
+  const size_t n_cols = (size_t)ctx->ds.n_nodes + 1;
   if (n_cols > b.col_cap) {
     b.col_cap = 0;
     if ((rc = grow(b.count, n_cols, 4)) || (rc = grow(b.col_off, n_cols, 4)) || (rc = grow(b.dabs, n_cols, 8)))
@@ -701,7 +485,7 @@ int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const
     b.col_cap = n_cols;
   }
   P.pairs = np.pairs;
-  P.n_nodes = ctx->n_nodes;
+  P.n_nodes = ctx->ds.n_nodes;
   P.es = np.es;
   P.src = np.src;
   P.n_node_total = ctx->n_node_total;
@@ -711,7 +495,7 @@ int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const
   P.cv_off = ctx->d_cv_off;
   P.disc_cv = np.disc_cv;
   P.n_cv = ctx->n_cv_total;
-  P.finite = ctx->corr_finite && ctx->disc_cv_finite;
+  P.finite = ctx->ds.corr_finite && ctx->disc_cv_finite;
   P.disc_wd = np.disc_wd;
   P.cv_shift = np.cv_shift;
   P.n_perm = (int32_t)n_perm;
@@ -745,7 +529,7 @@ int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const
 // direct sets when src.mode == NR_IDX_DIRECT, n_perm == 1) into d_out.
 int launch_batch(nr_ctx* ctx, const nr::IndexSource& src, int64_t n_perm, double* d_out, const Lane& ln) {
   const int n_stat = n_stat_of(ctx);
-  const bool data = ctx->d_data != nullptr;
+  const bool data = ctx->ds.d_data != nullptr;
   NR_HIP(ctx, hipSetDevice(ctx->device));
   int rc = fill_na(ctx, d_out, (int64_t)ctx->n_rows * n_stat * n_perm, ln.st);
   if (rc) return rc;
@@ -753,11 +537,11 @@ int launch_batch(nr_ctx* ctx, const nr::IndexSource& src, int64_t n_perm, double
   const int64_t n_items = (int64_t)ctx->n_present * n_perm;
 
   nr::NetParams np{};
-  np.pairs = ctx->d_pairs;
-  np.es = ctx->pairs_es;
-  np.colsum = ctx->d_colsum;
-  np.n_nodes = ctx->n_nodes;
-  np.symmetric = ctx->symmetric;
+  np.pairs = ctx->ds.d_pairs;
+  np.es = ctx->ds.pairs_es;
+  np.colsum = ctx->ds.d_colsum;
+  np.n_nodes = ctx->ds.n_nodes;
+  np.symmetric = ctx->ds.symmetric;
   np.src = src;
   np.node_off = ctx->d_node_off;
   np.cv_off = ctx->d_cv_off;
@@ -783,13 +567,13 @@ int launch_batch(nr_ctx* ctx, const nr::IndexSource& src, int64_t n_perm, double
   // which module on, in size order, it did). (Round 2 measured the network
   // phase fused into the profile items without the table at +0.7%, within
   // run-to-run noise, and on a concurrent stream at -11%.)
-  const bool table = data && ctx->pairs_es == 2;
+  const bool table = data && ctx->ds.pairs_es == 2;
   // Without the Gram table the network statistics of every present module
   // come from the column sweep (sweep.hip: each test column streamed into LDS
   // once per batch) where the shapes allow it (n < 65,536, modules of at most
   // 4,096 nodes); the item-major gather kernel otherwise. The choice depends
   // on the shapes only.
-  if (!table && nr::sweep_supported(ctx->n_nodes, ctx->k_max)) {
+  if (!table && nr::sweep_supported(ctx->ds.n_nodes, ctx->k_max)) {
     if (ln.timed) timer_begin(ctx, 0, ln.st);
     if ((rc = launch_sweep_batch(ctx, np, n_perm, ln))) return rc;
     if (ln.timed) timer_end(ctx, 0, n_items, ln.st);
@@ -802,13 +586,13 @@ int launch_batch(nr_ctx* ctx, const nr::IndexSource& src, int64_t n_perm, double
     if (ln.timed) timer_end(ctx, 0, (int64_t)n_mod * n_perm, ln.st);
     return NR_OK;
   };
-  if (!table && !nr::sweep_supported(ctx->n_nodes, ctx->k_max) && (rc = nets(ctx->n_present))) return rc;
+  if (!table && !nr::sweep_supported(ctx->ds.n_nodes, ctx->k_max) && (rc = nets(ctx->n_present))) return rc;
 
   if (data) {
     nr::ProfileParams pp{};
-    pp.data = ctx->d_data;
-    pp.n_samples = ctx->n_samples;
-    pp.ones_off = ctx->n_nodes * ctx->n_samples;
+    pp.data = ctx->ds.d_data;
+    pp.n_samples = ctx->ds.n_samples;
+    pp.ones_off = ctx->ds.n_nodes * ctx->ds.n_samples;
     pp.src = src;
     pp.node_off = ctx->d_node_off;
     pp.disc_nc = ctx->d_disc_nc;
@@ -855,8 +639,8 @@ int launch_batch(nr_ctx* ctx, const nr::IndexSource& src, int64_t n_perm, double
 constexpr int64_t kTableMaxElems = (int64_t)50000 * 50000;  // n <= 50,000: 140 GB during the build
 
 bool table_wanted(nr_ctx* ctx) {
-  if (!ctx->d_data || ctx->n_present == 0) return false;
-  const int64_t S = ctx->n_samples, n = ctx->n_nodes;
+  if (!ctx->ds.d_data || ctx->n_present == 0) return false;
+  const int64_t S = ctx->ds.n_samples, n = ctx->ds.n_nodes;
   if (n * n > kTableMaxElems) return false;
   double packed_w = 0.0, total_w = 0.0;
   int32_t packed_max = 0;
@@ -888,8 +672,8 @@ bool table_wanted(nr_ctx* ctx) {
 int maybe_build_table(nr_ctx* ctx) {
   if (ctx->table_checked == ctx->modules_serial) return NR_OK;
   ctx->table_checked = ctx->modules_serial;
-  if (ctx->pairs_es == 2 || !table_wanted(ctx)) return NR_OK;
-  const int64_t S = ctx->n_samples, n = ctx->n_nodes;
+  if (ctx->ds.pairs_es == 2 || !table_wanted(ctx)) return NR_OK;
+  const int64_t S = ctx->ds.n_samples, n = ctx->ds.n_nodes;
   const size_t nn = (size_t)n * (size_t)n;
   NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (ctx->obs_stream) NR_HIP(ctx, hipStreamSynchronize(ctx->obs_stream));
@@ -913,20 +697,20 @@ int maybe_build_table(nr_ctx* ctx) {
                     " MiB beside the resident matrices (40 bytes per matrix element; the table path is chosen "
                     "from the shapes, DESIGN.md section 5.2)");
   }
-  hipError_t e = nr::launch_gram_full(ctx->d_data, S, n, gram, cs, ctx->stream);
+  hipError_t e = nr::launch_gram_full(ctx->ds.d_data, S, n, gram, cs, ctx->stream);
   if (e == hipSuccess)
-    e = nr::launch_widen_pairs(ctx->d_pairs, gram, tab, n, ctx->symmetric, ctx->stream);
+    e = nr::launch_widen_pairs(ctx->ds.d_pairs, gram, tab, n, ctx->ds.symmetric, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {
     drop();
     return hip_fail(ctx, e, "Gram table");
   }
   dfree(gram);
-  dfree(ctx->d_pairs);
-  ctx->d_pairs = tab;
-  ctx->d_colsum = cs;
-  ctx->pairs_es = 2;
-  ctx->table_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+  dfree(ctx->ds.d_pairs);
+  ctx->ds.d_pairs = tab;
+  ctx->ds.d_colsum = cs;
+  ctx->ds.pairs_es = 2;
+  ctx->ds.table_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
   return NR_OK;
 }
 
@@ -936,16 +720,16 @@ int64_t auto_batch(const nr_ctx* ctx) {
   // launch tail (slots draining at different times) stays short: C3 at 1,024
   // permutations (51,200 items) per launch runs 3.5% faster than at 256
   // (profiles/r02/profile_variants.txt). Per-slot scratch does not depend on it.
-  const int64_t items_target = ctx->d_data ? 51200 : 65536;
+  const int64_t items_target = ctx->ds.d_data ? 51200 : 65536;
   int64_t b = std::max<int64_t>(1, items_target / std::max<int32_t>(ctx->n_present, 1));
-  if (ctx->d_data) {
+  if (ctx->ds.d_data) {
     // ... but launches of heavy modules stay short (~0.1 s), so progress and
     // interrupts keep their one-second cadence (src/thread-utils.cpp:49-82):
     // at most 2e12 Gram flops (2 S k min(S, k) per module) per launch; C3 at
     // 1,024 permutations is 1.7e12, C5 (k up to 2,000, S = 1,000) gets 66 (64 after the rounding below).
     double per_perm = 0.0;
     for (const int32_t k : ctx->order_k_h) {
-      const double kk = (double)k, s = (double)ctx->n_samples;
+      const double kk = (double)k, s = (double)ctx->ds.n_samples;
       per_perm += 2.0 * s * kk * std::min(s, kk);
     }
     if (per_perm > 0.0) b = std::min<int64_t>(b, std::max<int64_t>(1, (int64_t)(2e12 / per_perm)));
@@ -959,7 +743,7 @@ int64_t auto_batch(const nr_ctx* ctx) {
 }
 
 int check_ready(nr_ctx* ctx, bool need_null) {
-  if (!ctx->d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset: call nr_set_dataset first");
+  if (!ctx->ds.d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset: call nr_set_dataset first");
   if (ctx->n_rows <= 0) return fail(ctx, NR_ERR_INVALID, "no modules: call nr_set_modules first");
   if (ctx->modules_gen != ctx->data_gen)
     return fail(ctx, NR_ERR_INVALID, "the modules were set for another dataset: call nr_set_modules again");
@@ -1158,10 +942,7 @@ void nr_ctx_destroy(nr_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  sync_obs(ctx);
-  dfree(ctx->d_pairs);
-  dfree(ctx->d_data);
-  dfree(ctx->d_colsum);
+  reset_dataset(ctx);
   dfree(ctx->d_row_of);
   dfree(ctx->d_node_off);
   dfree(ctx->d_cv_off);
@@ -1230,15 +1011,9 @@ int nr_ctx_set_host_threads(nr_ctx* ctx, int n) {
   return NR_OK;
 }
 
-int nr_h2d_bytes(int64_t* bytes) {
-  if (!bytes) return NR_ERR_INVALID;
-  *bytes = g_h2d_bytes.load();
-  return NR_OK;
-}
+}  // extern "C"
 
-// Copy n doubles with up to `threads` host threads (pageable -> pinned staging).
-static void parallel_copy(double* dst, const double* src, int64_t n, int threads,
-                          int64_t min_part = (int64_t)1 << 20 /* 8 MiB per thread at least */) {
+void parallel_copy(double* dst, const double* src, int64_t n, int threads, int64_t min_part) {
   const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(threads, n / min_part));
   if (nt == 1) {
     std::memcpy(dst, src, (size_t)n * sizeof(double));
@@ -1280,631 +1055,7 @@ static void parallel_copy2(double* d1, const double* s1, int64_t n1, double* d2,
   for (auto& x : th) x.join();
 }
 
-// Host matrices to HBM through pinned, double-buffered chunks: host threads
-// fill pinned buffer b with chunk i+1 (from the caller's pageable arrays)
-// while the copy engine moves chunk i and, for the corr/net pair, the
-// interleave kernel packs it into the {corr, net} layout. `net` NULL: a plain
-// copy of `corr` into `dst_plain`. net == corr (NetProps: the network doubles
-// as the unused correlation operand): the matrix crosses PCIe once and fills
-// both halves of the pairs.
-static int upload_pinned(nr_ctx* ctx, const double* corr, const double* net, int64_t n_elem, double2* dst_pairs,
-                         double* dst_plain, hipStream_t st) {
-  const bool same = net != nullptr && net == corr;
-  const int parts = net && !same ? 2 : 1;
-  const int threads = ctx->host_threads;
-  const int64_t chunk = std::min<int64_t>(n_elem, (int64_t)1 << 23);  // 64 MiB per matrix per chunk
-  double* h[2] = {nullptr, nullptr};
-  double* d[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int b = 0; b < 2 && e == hipSuccess; ++b) {
-    e = hipHostMalloc((void**)&h[b], (size_t)(parts * chunk) * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess && net) e = hipMalloc((void**)&d[b], (size_t)(parts * chunk) * sizeof(double));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[b], hipEventDisableTiming);
-  }
-  int64_t i = 0;
-  for (int64_t o = 0; o < n_elem && e == hipSuccess; o += chunk, ++i) {
-    const int b = (int)(i & 1);
-    const int64_t len = std::min(chunk, n_elem - o);
-    if (i >= 2) e = hipEventSynchronize(ev[b]);  // chunk i-2 has left buffer b
-    if (e != hipSuccess) break;
-    parallel_copy(h[b], corr + o, len, threads);
-    if (parts == 2) parallel_copy(h[b] + chunk, net + o, len, threads);
-    if (net) {
-      e = h2d_async(d[b], h[b], (size_t)len * sizeof(double), st);
-      if (e == hipSuccess && parts == 2) e = h2d_async(d[b] + chunk, h[b] + chunk, (size_t)len * sizeof(double), st);
-      if (e == hipSuccess) e = nr::launch_interleave(d[b], parts == 2 ? d[b] + chunk : d[b], dst_pairs + o, len, st);
-    } else {
-      e = h2d_async(dst_plain + o, h[b], (size_t)len * sizeof(double), st);
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[b], st);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  for (int b = 0; b < 2; ++b) {
-    if (h[b]) (void)hipHostFree(h[b]);
-    if (d[b]) (void)hipFree(d[b]);
-    if (ev[b]) (void)hipEventDestroy(ev[b]);
-  }
-  if (e != hipSuccess) return hip_fail(ctx, e, "dataset upload");
-  return NR_OK;
-}
-
-namespace {
-int set_dataset_impl(nr_ctx* ctx, const double* corr, const double* net, const double* data,
-                     int64_t n_nodes, int64_t n_samples, int where, int flags);
-}
-
-int nr_set_dataset(nr_ctx* ctx, const double* corr, const double* net, const double* data,
-                   int64_t n_nodes, int64_t n_samples, int where) {
-  return nr_set_dataset_ex(ctx, corr, net, data, n_nodes, n_samples, where, 0);
-}
-
-int nr_set_dataset_ex(nr_ctx* ctx, const double* corr, const double* net, const double* data,
-                      int64_t n_nodes, int64_t n_samples, int where, int flags) {
-  if (!ctx) return NR_ERR_INVALID;
-  if (flags & ~NR_SCALE_DATA) return fail(ctx, NR_ERR_INVALID, "unknown nr_set_dataset_ex flags");
-  if (!corr || !net || n_nodes <= 0) return fail(ctx, NR_ERR_INVALID, "corr/net missing or n_nodes <= 0");
-  if (data && n_samples < 2) return fail(ctx, NR_ERR_INVALID, "data needs n_samples >= 2");
-  if (n_nodes > (int64_t)INT32_MAX) return fail(ctx, NR_ERR_UNSUPPORTED, "n_nodes exceeds 2^31-1");
-  NR_HIP(ctx, hipSetDevice(ctx->device));
-  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  reset_dataset(ctx);
-  const int rc = set_dataset_impl(ctx, corr, net, data, n_nodes, n_samples, where, flags);
-  if (rc != NR_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    reset_dataset(ctx);
-  }
-  return rc;
-}
-
-namespace {
-int set_dataset_impl(nr_ctx* ctx, const double* corr, const double* net, const double* data,
-                     int64_t n_nodes, int64_t n_samples, int where, int flags) {
-  const int64_t n_elem = n_nodes * n_nodes;
-  NR_HIP(ctx, hipMalloc((void**)&ctx->d_pairs, (size_t)n_elem * sizeof(double2)));
-  if (where == NR_DEVICE) {
-    NR_HIP(ctx, nr::launch_interleave(corr, net, ctx->d_pairs, n_elem, ctx->stream));
-  } else {
-    const int rc = upload_pinned(ctx, corr, net, n_elem, ctx->d_pairs, nullptr, ctx->stream);
-    if (rc) return rc;
-  }
-  NR_HIP(ctx, hipMemsetAsync(ctx->d_counters + 5, 0, sizeof(int), ctx->stream));
-  NR_HIP(ctx, nr::launch_symmetry(ctx->d_pairs, n_nodes, ctx->d_counters + 5, ctx->stream));
-  int asym = 0;
-  NR_HIP(ctx, hipMemcpyAsync(&asym, ctx->d_counters + 5, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  if (data) {
-    const size_t bytes = (size_t)(n_samples * n_nodes) * sizeof(double);
-    NR_HIP(ctx, hipMalloc((void**)&ctx->d_data, bytes + 2 * (size_t)n_samples * sizeof(double)));
-    if (int rc = fill_virtual_columns(ctx, n_nodes, n_samples)) return rc;
-    // NR_SCALE_DATA: the raw data goes to a device buffer and is scaled there
-    // (Scale, src/scale.cpp:14-25) straight into the resident block
-    double* raw = nullptr;
-    if (flags & NR_SCALE_DATA) NR_HIP(ctx, hipMalloc((void**)&raw, bytes));
-    double* dst = raw ? raw : ctx->d_data;
-    int rc = NR_OK;
-    if (where == NR_DEVICE) {
-      const hipError_t e = hipMemcpyAsync(dst, data, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-      if (e != hipSuccess) rc = hip_fail(ctx, e, "data copy");
-    } else {
-      rc = upload_pinned(ctx, data, nullptr, n_samples * n_nodes, nullptr, dst, ctx->stream);
-    }
-    if (!rc && raw) {
-      hipError_t e = nr::launch_scale(raw, ctx->d_data, n_samples, n_nodes, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-      if (e != hipSuccess) rc = hip_fail(ctx, e, "scale");
-    }
-    if (raw) (void)hipFree(raw);
-    if (rc) return rc;
-  }
-  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->symmetric = (asym & 1) ? 0 : 1;
-  ctx->corr_finite = (asym & 2) ? 0 : 1;
-  ctx->net_finite = (asym & 4) ? 0 : 1;
-  ctx->n_nodes = n_nodes;
-  ctx->n_samples = data ? n_samples : 0;
-  return NR_OK;
-}
-}  // namespace
-
-// ---- the from-data path ---------------------------------------------------
-
-namespace {
-int set_dataset_from_data_impl(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples, int where,
-                               int flags, int net_type, double beta) {
-  const size_t pair_bytes = (size_t)n_nodes * (size_t)n_nodes * sizeof(double2);
-  if (hipMalloc((void**)&ctx->d_pairs, pair_bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    ctx->d_pairs = nullptr;
-    return fail(ctx, NR_ERR_OOM,
-                "from-data dataset: allocation of the " + std::to_string(pair_bytes >> 20) +
-                    " MiB {corr, net} array failed (16 bytes per matrix element)");
-  }
-  const size_t bytes = (size_t)(n_samples * n_nodes) * sizeof(double);
-  NR_HIP(ctx, hipMalloc((void**)&ctx->d_data, bytes + 2 * (size_t)n_samples * sizeof(double)));
-  if (int rc = fill_virtual_columns(ctx, n_nodes, n_samples)) return rc;
-  double* raw = nullptr;
-  if (flags & NR_SCALE_DATA) NR_HIP(ctx, hipMalloc((void**)&raw, bytes));
-  double* dst = raw ? raw : ctx->d_data;
-  int rc = NR_OK;
-  if (where == NR_DEVICE) {
-    const hipError_t e = hipMemcpyAsync(dst, data, bytes, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) rc = hip_fail(ctx, e, "data copy");
-  } else {
-    rc = upload_pinned(ctx, data, nullptr, n_samples * n_nodes, nullptr, dst, ctx->stream);
-  }
-  if (!rc && raw) {
-    hipError_t e = nr::launch_scale(raw, ctx->d_data, n_samples, n_nodes, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = hip_fail(ctx, e, "scale");
-  }
-  if (raw) (void)hipFree(raw);
-  if (rc) return rc;
-
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipEventCreate(&ev[0]);
-  if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-  int bad = 0;
-  float ms = 0.f;
-  if (e == hipSuccess) e = hipMemsetAsync(ctx->d_counters + 5, 0, sizeof(int), ctx->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[0], ctx->stream);
-  if (e == hipSuccess)
-    e = nr::launch_netbuild(ctx->d_data, n_samples, n_nodes, ctx->d_pairs, net_type, beta, ctx->d_counters + 5,
-                            ctx->stream);
-  if (e == hipSuccess) e = hipEventRecord(ev[1], ctx->stream);
-  if (e == hipSuccess)
-    e = hipMemcpyAsync(&bad, ctx->d_counters + 5, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-  for (hipEvent_t x : ev)
-    if (x) (void)hipEventDestroy(x);
-  if (e != hipSuccess) return hip_fail(ctx, e, "from-data build");
-  ctx->netbuild_ms = (double)ms;
-  ctx->symmetric = 1;  // every tile is stored and mirrored from the same bits
-  ctx->corr_finite = (bad & 2) ? 0 : 1;
-  ctx->net_finite = (bad & 4) ? 0 : 1;
-  ctx->n_nodes = n_nodes;
-  ctx->n_samples = n_samples;
-  return NR_OK;
-}
-}  // namespace
-
-int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples, int where,
-                             int flags, int net_type, double beta) {
-  if (!ctx) return NR_ERR_INVALID;
-  if (flags & ~NR_SCALE_DATA) return fail(ctx, NR_ERR_INVALID, "unknown nr_set_dataset_from_data flags");
-  if (!data) return fail(ctx, NR_ERR_INVALID, "data missing");
-  if (n_nodes < 1 || n_samples < 2) return fail(ctx, NR_ERR_INVALID, "data needs n_nodes >= 1 and n_samples >= 2");
-  if (where != NR_HOST && where != NR_DEVICE) return fail(ctx, NR_ERR_INVALID, "where must be NR_HOST or NR_DEVICE");
-  if (net_type != NR_NET_UNSIGNED && net_type != NR_NET_SIGNED && net_type != NR_NET_SIGNED_HYBRID)
-    return fail(ctx, NR_ERR_INVALID, "unknown network type");
-  if (!std::isfinite(beta) || beta <= 0.0) return fail(ctx, NR_ERR_INVALID, "beta must be finite and > 0");
-  if (n_nodes > (int64_t)INT32_MAX) return fail(ctx, NR_ERR_UNSUPPORTED, "n_nodes exceeds 2^31-1");
-  NR_HIP(ctx, hipSetDevice(ctx->device));
-  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  reset_dataset(ctx);
-  const int rc = set_dataset_from_data_impl(ctx, data, n_nodes, n_samples, where, flags, net_type, beta);
-  if (rc != NR_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    reset_dataset(ctx);
-  }
-  return rc;
-}
-
-int nr_netbuild_ms(nr_ctx* ctx, double* ms) {
-  if (!ctx || !ms) return NR_ERR_INVALID;
-  *ms = ctx->d_pairs ? ctx->netbuild_ms : 0.0;
-  return NR_OK;
-}
-
-int nr_get_dataset_matrices(nr_ctx* ctx, double* corr_out, double* net_out) {
-  if (!ctx) return NR_ERR_INVALID;
-  if (!ctx->d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
-  if (!corr_out && !net_out) return NR_OK;
-  NR_HIP(ctx, hipSetDevice(ctx->device));
-  // the table build replaces d_pairs between launches only; wait for both lanes
-  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->obs_stream) NR_HIP(ctx, hipStreamSynchronize(ctx->obs_stream));
-  const int64_t n_elem = ctx->n_nodes * ctx->n_nodes;
-  const int64_t chunk = std::min<int64_t>(n_elem, (int64_t)1 << 22);  // 32 MiB per matrix per chunk
-  const int parts = (corr_out ? 1 : 0) + (net_out ? 1 : 0);
-  double* d = nullptr;
-  NR_HIP(ctx, hipMalloc((void**)&d, (size_t)(parts * chunk) * sizeof(double)));
-  double* dc = corr_out ? d : nullptr;
-  double* dn = net_out ? d + (corr_out ? chunk : 0) : nullptr;
-  hipError_t e = hipSuccess;
-  for (int64_t o = 0; o < n_elem && e == hipSuccess; o += chunk) {
-    const int64_t len = std::min(chunk, n_elem - o);
-    e = nr::launch_deinterleave(ctx->d_pairs, ctx->pairs_es, o, len, dc, dn, ctx->stream);
-    if (e == hipSuccess && dc)
-      e = hipMemcpyAsync(corr_out + o, dc, (size_t)len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && dn)
-      e = hipMemcpyAsync(net_out + o, dn, (size_t)len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // the staging buffer is free again
-  }
-  (void)hipFree(d);
-  if (e != hipSuccess) return hip_fail(ctx, e, "matrix export");
-  return NR_OK;
-}
-
-// File -> pinned -> HBM for one matrix payload: the host inflates / reads
-// straight into pinned buffer b while the copy engine moves the previous one
-// and a kernel converts it from XDR into `pairs` (half 0 / 1) or `plain`.
-static int upload_file_matrix(nr_ctx* ctx, nr::RMatrixReader& rd, double2* pairs, int half, double* plain,
-                              hipStream_t st) {
-  const int64_t n = rd.length();
-  const int64_t chunk = std::min<int64_t>(std::max<int64_t>(n, 1), (int64_t)1 << 23);  // 64 MiB
-  double* h[2] = {nullptr, nullptr};
-  double* d[2] = {nullptr, nullptr};
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  hipError_t e = hipSuccess;
-  for (int b = 0; b < 2 && e == hipSuccess; ++b) {
-    e = hipHostMalloc((void**)&h[b], (size_t)chunk * sizeof(double), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipMalloc((void**)&d[b], (size_t)chunk * sizeof(double));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[b], hipEventDisableTiming);
-  }
-  bool read_ok = true;
-  int64_t i = 0;
-  for (int64_t o = 0; o < n && e == hipSuccess && read_ok; o += chunk, ++i) {
-    const int b = (int)(i & 1);
-    const int64_t len = std::min(chunk, n - o);
-    if (i >= 2) e = hipEventSynchronize(ev[b]);
-    if (e != hipSuccess) break;
-    read_ok = rd.read_raw(h[b], len);
-    if (!read_ok) break;
-    e = h2d_async(d[b], h[b], (size_t)len * sizeof(double), st);
-    if (e == hipSuccess) e = nr::launch_xdr(d[b], pairs ? pairs + o : nullptr, half, plain ? plain + o : nullptr, len, st);
-    if (e == hipSuccess) e = hipEventRecord(ev[b], st);
-  }
-  const hipError_t e2 = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = e2;
-  for (int b = 0; b < 2; ++b) {
-    if (h[b]) (void)hipHostFree(h[b]);
-    if (d[b]) (void)hipFree(d[b]);
-    if (ev[b]) (void)hipEventDestroy(ev[b]);
-  }
-  if (!read_ok) return fail(ctx, NR_ERR_INVALID, rd.error());
-  if (e != hipSuccess) return hip_fail(ctx, e, "file upload");
-  return NR_OK;
-}
-
-namespace {
-int set_dataset_files_impl(nr_ctx* ctx, const char* corr_path, const char* net_path, const char* data_path,
-                           const char* corr_object, const char* net_object, const char* data_object,
-                           int scale_data) {
-  nr::RMatrixReader rc_, rn_;
-  if (!rc_.open(corr_path, corr_object)) return fail(ctx, NR_ERR_INVALID, std::string(corr_path) + ": " + rc_.error());
-  if (!rn_.open(net_path, net_object)) return fail(ctx, NR_ERR_INVALID, std::string(net_path) + ": " + rn_.error());
-  const int64_t n_elem = rc_.length();
-  int64_t n_nodes = (int64_t)std::llround(std::sqrt((double)n_elem));
-  if (n_nodes <= 0 || n_nodes * n_nodes != n_elem) return fail(ctx, NR_ERR_INVALID, "correlation matrix is not square");
-  if (rn_.length() != n_elem) return fail(ctx, NR_ERR_INVALID, "network and correlation matrices differ in size");
-  if (n_nodes > (int64_t)INT32_MAX) return fail(ctx, NR_ERR_UNSUPPORTED, "n_nodes exceeds 2^31-1");
-  NR_HIP(ctx, hipMalloc((void**)&ctx->d_pairs, (size_t)n_elem * sizeof(double2)));
-  int rc;
-  nr::RMatrixMeta mc, mn;
-  if ((rc = upload_file_matrix(ctx, rc_, ctx->d_pairs, 0, nullptr, ctx->stream))) return rc;
-  if (!rc_.finish(&mc)) return fail(ctx, NR_ERR_INVALID, std::string(corr_path) + ": " + rc_.error());
-  if ((rc = upload_file_matrix(ctx, rn_, ctx->d_pairs, 1, nullptr, ctx->stream))) return rc;
-  if (!rn_.finish(&mn)) return fail(ctx, NR_ERR_INVALID, std::string(net_path) + ": " + rn_.error());
-  if (mc.nrow != n_nodes || mc.ncol != n_nodes || mn.nrow != n_nodes || mn.ncol != n_nodes)
-    return fail(ctx, NR_ERR_INVALID, "correlation / network matrices must be square and of one size");
-  // R/check-user-input.R:750-771: row and column names of each square matrix
-  // agree, and the node order is the same in correlation, network and data
-  if ((!mc.rownames.empty() && !mc.colnames.empty() && mc.rownames != mc.colnames) ||
-      (!mn.rownames.empty() && !mn.colnames.empty() && mn.rownames != mn.colnames))
-    return fail(ctx, NR_ERR_INVALID, "mismatch between row and column names in 'correlation' / 'network'");
-  if (!mc.colnames.empty() && !mn.colnames.empty() && mc.colnames != mn.colnames)
-    return fail(ctx, NR_ERR_INVALID, "mismatch in node order between 'data', 'correlation', and 'network'");
-  const std::vector<std::string> names = !mn.colnames.empty() ? mn.colnames : mc.colnames;
-  int64_t n_samples = 0;
-  if (data_path) {
-    nr::RMatrixReader rd;
-    if (!rd.open(data_path, data_object)) return fail(ctx, NR_ERR_INVALID, std::string(data_path) + ": " + rd.error());
-    if (rd.length() % n_nodes != 0) return fail(ctx, NR_ERR_INVALID, "data matrix columns do not match the network");
-    n_samples = rd.length() / n_nodes;
-    if (n_samples < 2) return fail(ctx, NR_ERR_INVALID, "data needs n_samples >= 2");
-    double* raw = nullptr;
-    NR_HIP(ctx, hipMalloc((void**)&raw, (size_t)rd.length() * sizeof(double)));
-    rc = upload_file_matrix(ctx, rd, nullptr, 0, raw, ctx->stream);
-    nr::RMatrixMeta md;
-    if (!rc && !rd.finish(&md)) rc = fail(ctx, NR_ERR_INVALID, std::string(data_path) + ": " + rd.error());
-    if (!rc && (md.nrow != n_samples || md.ncol != n_nodes))
-      rc = fail(ctx, NR_ERR_INVALID, "data matrix must be samples x nodes");
-    if (!rc && !md.colnames.empty() && !names.empty() && md.colnames != names)
-      rc = fail(ctx, NR_ERR_INVALID, "mismatch in node order between 'data', 'correlation', and 'network'");
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMalloc((void**)&ctx->d_data, (size_t)(n_samples * (n_nodes + 2)) * sizeof(double));
-    // Scale (src/scale.cpp:14-25) on the device, as the R code scales after loading
-    if (!rc && e == hipSuccess)
-      e = scale_data ? nr::launch_scale(raw, ctx->d_data, n_samples, n_nodes, ctx->stream)
-                     : hipMemcpyAsync(ctx->d_data, raw, (size_t)(n_samples * n_nodes) * sizeof(double),
-                                      hipMemcpyDeviceToDevice, ctx->stream);
-    if (!rc && e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(raw);
-    if (rc) return rc;
-    if (e != hipSuccess) return hip_fail(ctx, e, "data upload");
-    if ((rc = fill_virtual_columns(ctx, n_nodes, n_samples))) return rc;
-  }
-  NR_HIP(ctx, hipMemsetAsync(ctx->d_counters + 5, 0, sizeof(int), ctx->stream));
-  NR_HIP(ctx, nr::launch_symmetry(ctx->d_pairs, n_nodes, ctx->d_counters + 5, ctx->stream));
-  int asym = 0;
-  NR_HIP(ctx, hipMemcpyAsync(&asym, ctx->d_counters + 5, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->symmetric = (asym & 1) ? 0 : 1;
-  ctx->corr_finite = (asym & 2) ? 0 : 1;
-  ctx->net_finite = (asym & 4) ? 0 : 1;
-  // committed only once everything above has succeeded
-  ctx->node_names = names;
-  ctx->n_nodes = n_nodes;
-  ctx->n_samples = n_samples;
-  return NR_OK;
-}
-}  // namespace
-
-int nr_set_dataset_files(nr_ctx* ctx, const char* corr_path, const char* net_path, const char* data_path,
-                         const char* corr_object, const char* net_object, const char* data_object,
-                         int scale_data) {
-  if (!ctx) return NR_ERR_INVALID;
-  if (!corr_path || !net_path) return fail(ctx, NR_ERR_INVALID, "corr/net file missing");
-  NR_HIP(ctx, hipSetDevice(ctx->device));
-  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  // The old dataset is dropped first; on any failure the context is left with
-  // no dataset at all (never a new buffer with the old shape), and modules
-  // set for the old dataset are invalidated either way.
-  reset_dataset(ctx);
-  int rc;
-  try {
-    rc = set_dataset_files_impl(ctx, corr_path, net_path, data_path, corr_object, net_object, data_object,
-                                scale_data);
-  } catch (const std::bad_alloc&) {
-    rc = fail(ctx, NR_ERR_OOM, "host memory allocation failed");
-  } catch (const std::exception& ex) {
-    rc = fail(ctx, NR_ERR_INVALID, std::string("internal error: ") + ex.what());
-  }
-  if (rc != NR_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
-    reset_dataset(ctx);
-  }
-  return rc;
-}
-
-int nr_dataset_shape(const nr_ctx* ctx, int64_t* n_nodes, int64_t* n_samples) {
-  if (!ctx) return NR_ERR_INVALID;
-  if (n_nodes) *n_nodes = ctx->n_nodes;
-  if (n_samples) *n_samples = ctx->n_samples;
-  return NR_OK;
-}
-
-int nr_dataset_colnames(const nr_ctx* ctx, char* buf, int64_t cap, int64_t* needed) {
-  if (!ctx || !needed) return NR_ERR_INVALID;
-  int64_t total = 0;
-  for (const std::string& s : ctx->node_names) total += (int64_t)s.size() + 1;
-  *needed = total;
-  if (!buf || cap < total) return NR_OK;
-  for (const std::string& s : ctx->node_names) {
-    std::memcpy(buf, s.c_str(), s.size() + 1);
-    buf += s.size() + 1;
-  }
-  return NR_OK;
-}
-
-int nr_copy_dataset(nr_ctx* dst, const nr_ctx* src) {
-  if (!dst || !src || dst == src) return NR_ERR_INVALID;
-  if (!src->d_pairs) return fail(dst, NR_ERR_INVALID, "source context has no dataset");
-  NR_HIP(dst, hipSetDevice(dst->device));
-  NR_HIP(dst, hipStreamSynchronize(dst->stream));
-  reset_dataset(dst);  // on a failure below dst is left with no dataset
-  const size_t pair_bytes = pair_bytes_of(src);
-  NR_HIP(dst, hipMalloc((void**)&dst->d_pairs, pair_bytes));
-  if (src->d_colsum) NR_HIP(dst, hipMalloc((void**)&dst->d_colsum, (size_t)src->n_nodes * sizeof(double)));
-  const size_t data_bytes = (size_t)(src->n_samples * (src->n_nodes + 2)) * sizeof(double);  // + virtual columns
-  if (src->d_data) NR_HIP(dst, hipMalloc((void**)&dst->d_data, data_bytes));
-  // Device to device: over xGMI between GPUs, an on-device copy when both
-  // contexts share a GPU. The source must be idle (its upload synchronised).
-  NR_HIP(dst, hipMemcpyPeerAsync(dst->d_pairs, dst->device, src->d_pairs, src->device, pair_bytes, dst->stream));
-  if (src->d_data)
-    NR_HIP(dst, hipMemcpyPeerAsync(dst->d_data, dst->device, src->d_data, src->device, data_bytes, dst->stream));
-  if (src->d_colsum)
-    NR_HIP(dst, hipMemcpyPeerAsync(dst->d_colsum, dst->device, src->d_colsum, src->device,
-                                   (size_t)src->n_nodes * sizeof(double), dst->stream));
-  NR_HIP(dst, hipStreamSynchronize(dst->stream));
-  dst->pairs_es = src->pairs_es;
-  dst->n_nodes = src->n_nodes;
-  dst->n_samples = src->n_samples;
-  dst->node_names = src->node_names;
-  dst->symmetric = src->symmetric;
-  dst->corr_finite = src->corr_finite;
-  dst->net_finite = src->net_finite;
-  return NR_OK;
-}
-
-// One resident dataset to n - 1 other contexts ("broadcast once
-// per test dataset"), bandwidth-optimal on a full xGMI mesh: a scatter and an
-// all-gather of peer copies. Each buffer is cut into n - 1 pieces. Phase 1:
-// piece p goes from the source to context p + 1 (every source link busy at
-// once, B / (n-1) bytes each). Phase 2: context p + 1 forwards piece p to the
-// other n - 2 destinations over its own direct links, each copy behind the
-// event that marks the piece's arrival. Every link carries at most
-// B / (n-1) per phase: 2B / ((n-1) L) in all, against B / L for a direct
-// fan-out (each destination pulls all B over its one link to the source) or
-// a single pipelined ring (DESIGN.md section 7 has the arithmetic). The source
-// must be idle; on failure every destination is left with no dataset.
-// Peer access between every pair of distinct GPUs a broadcast uses, in both
-// directions (the scatter reads GPU 0 from each destination's stream, the
-// all-gather reads every destination from every other): direct copies over
-// the xGMI links instead of copies staged through host memory
-// (src/permutations.cpp:335-380 is the reference's one-process parallel
-// section this replaces). Enabled once per ordered pair per process. A pair
-// without peer access still works -- hipMemcpyPeerAsync stages it through
-// host memory -- at PCIe speed; such pairs are recorded
-// (nr_peer_staged_pairs) instead of failing the broadcast.
-static std::mutex g_peer_mu;
-static std::set<std::pair<int, int>> g_peer_on, g_peer_staged;
-
-static int enable_peer_access(nr_ctx* err_ctx, const std::vector<int>& devs) {
-  std::lock_guard<std::mutex> lk(g_peer_mu);
-  for (int a : devs)
-    for (int b : devs) {
-      if (a == b || g_peer_on.count({a, b}) || g_peer_staged.count({a, b})) continue;
-      int can = 0;
-      NR_HIP(err_ctx, hipDeviceCanAccessPeer(&can, a, b));
-      if (!can) {
-        g_peer_staged.insert({a, b});
-        continue;
-      }
-      NR_HIP(err_ctx, hipSetDevice(a));
-      const hipError_t e = hipDeviceEnablePeerAccess(b, 0);
-      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) return hip_fail(err_ctx, e, "hipDeviceEnablePeerAccess");
-      (void)hipGetLastError();  // clears hipErrorPeerAccessAlreadyEnabled
-      g_peer_on.insert({a, b});
-    }
-  return NR_OK;
-}
-
-int nr_peer_staged_pairs(int* n) {
-  if (!n) return NR_ERR_INVALID;
-  std::lock_guard<std::mutex> lk(g_peer_mu);
-  *n = (int)g_peer_staged.size();
-  return NR_OK;
-}
-
-// The calling thread's current device, restored on every return path.
-struct DeviceRestore {
-  int dev = -1;
-  DeviceRestore() {
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  }
-  ~DeviceRestore() {
-    if (dev >= 0) (void)hipSetDevice(dev);
-  }
-};
-
-int nr_broadcast_dataset(nr_ctx* const* ctxs, int n) {
-  if (!ctxs || n < 1) return NR_ERR_INVALID;
-  DeviceRestore restore;
-  nr_ctx* src = ctxs[0];
-  if (!src) return NR_ERR_INVALID;
-  for (int g = 1; g < n; ++g)
-    for (int h = 0; h < g; ++h)
-      if (!ctxs[g] || ctxs[g] == ctxs[h]) return fail(src, NR_ERR_INVALID, "broadcast: contexts must be distinct");
-  if (!src->d_pairs) return fail(src, NR_ERR_INVALID, "source context has no dataset");
-  if (n == 1) return NR_OK;
-  {
-    std::vector<int> devs;
-    for (int g = 0; g < n; ++g)
-      if (std::find(devs.begin(), devs.end(), ctxs[g]->device) == devs.end()) devs.push_back(ctxs[g]->device);
-    if (int rc = enable_peer_access(src, devs)) return rc;
-  }
-  const int parts = n - 1;
-  struct Buf {
-    const char* s;
-    std::vector<char*> d;
-    size_t bytes;
-  };
-  std::vector<Buf> bufs;
-  const size_t pair_bytes = pair_bytes_of(src);
-  const size_t data_bytes = (size_t)(src->n_samples * (src->n_nodes + 2)) * sizeof(double);  // + virtual columns
-  const size_t cs_bytes = (size_t)src->n_nodes * sizeof(double);
-  bufs.push_back({reinterpret_cast<const char*>(src->d_pairs), std::vector<char*>(n, nullptr), pair_bytes});
-  if (src->d_data) bufs.push_back({reinterpret_cast<const char*>(src->d_data), std::vector<char*>(n, nullptr), data_bytes});
-  if (src->d_colsum)
-    bufs.push_back({reinterpret_cast<const char*>(src->d_colsum), std::vector<char*>(n, nullptr), cs_bytes});
-  auto clear_all = [&]() {
-    for (int g = 1; g < n; ++g) {
-      (void)hipSetDevice(ctxs[g]->device);
-      (void)hipStreamSynchronize(ctxs[g]->stream);
-      reset_dataset(ctxs[g]);
-    }
-  };
-  for (int g = 1; g < n; ++g) {
-    nr_ctx* d = ctxs[g];
-    NR_HIP(d, hipSetDevice(d->device));
-    NR_HIP(d, hipStreamSynchronize(d->stream));
-    reset_dataset(d);
-    hipError_t e = hipMalloc((void**)&d->d_pairs, pair_bytes);
-    if (e == hipSuccess && src->d_data) e = hipMalloc((void**)&d->d_data, data_bytes);
-    if (e == hipSuccess && src->d_colsum) e = hipMalloc((void**)&d->d_colsum, cs_bytes);
-    if (e != hipSuccess) {
-      const int rc = hip_fail(d, e, "broadcast allocation");
-      clear_all();
-      return fail(src, rc, d->err);
-    }
-    size_t b = 0;
-    bufs[b++].d[g] = reinterpret_cast<char*>(d->d_pairs);
-    if (src->d_data) bufs[b++].d[g] = reinterpret_cast<char*>(d->d_data);
-    if (src->d_colsum) bufs[b++].d[g] = reinterpret_cast<char*>(d->d_colsum);
-  }
-  auto piece = [&](size_t bytes, int p, size_t* a, size_t* len) {
-    const size_t per = ((bytes + parts - 1) / parts + 255) / 256 * 256;
-    *a = std::min(bytes, (size_t)p * per);
-    *len = std::min(bytes, *a + per) - *a;
-  };
-  NR_HIP(src, hipSetDevice(src->device));
-  NR_HIP(src, hipStreamSynchronize(src->stream));
-  std::vector<hipEvent_t> ev(parts, nullptr);
-  hipError_t e = hipSuccess;
-  // phase 1: the scatter
-  for (int p = 0; p < parts && e == hipSuccess; ++p) {
-    nr_ctx* d = ctxs[p + 1];
-    e = hipSetDevice(d->device);
-    for (const Buf& bf : bufs) {
-      size_t a, len;
-      piece(bf.bytes, p, &a, &len);
-      if (e == hipSuccess && len)
-        e = hipMemcpyPeerAsync(bf.d[p + 1] + a, d->device, bf.s + a, src->device, len, d->stream);
-    }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ev[p], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventRecord(ev[p], d->stream);
-  }
-  // phase 2: the all-gather among the destinations
-  for (int g = 1; g < n && e == hipSuccess; ++g) {
-    nr_ctx* d = ctxs[g];
-    e = hipSetDevice(d->device);
-    for (int p = 0; p < parts && e == hipSuccess; ++p) {
-      if (p == g - 1) continue;
-      e = hipStreamWaitEvent(d->stream, ev[p], 0);
-      for (const Buf& bf : bufs) {
-        size_t a, len;
-        piece(bf.bytes, p, &a, &len);
-        if (e == hipSuccess && len)
-          e = hipMemcpyPeerAsync(bf.d[g] + a, d->device, bf.d[p + 1] + a, ctxs[p + 1]->device, len, d->stream);
-      }
-    }
-  }
-  for (int g = 1; g < n; ++g) {
-    const hipError_t e2 = hipSetDevice(ctxs[g]->device);
-    const hipError_t e3 = hipStreamSynchronize(ctxs[g]->stream);
-    if (e == hipSuccess) e = e2 != hipSuccess ? e2 : e3;
-  }
-  for (hipEvent_t x : ev)
-    if (x) (void)hipEventDestroy(x);
-  if (e != hipSuccess) {
-    const int rc = hip_fail(src, e, "dataset broadcast");
-    clear_all();
-    return rc;
-  }
-  for (int g = 1; g < n; ++g) {
-    nr_ctx* d = ctxs[g];
-    d->pairs_es = src->pairs_es;
-    d->n_nodes = src->n_nodes;
-    d->n_samples = src->n_samples;
-    d->node_names = src->node_names;
-    d->symmetric = src->symmetric;
-    d->corr_finite = src->corr_finite;
-    d->net_finite = src->net_finite;
-    d->table_ms = src->table_ms;
-  }
-  return NR_OK;
-}
-
-int nr_clear_dataset(nr_ctx* ctx) {
-  if (!ctx) return NR_ERR_INVALID;
-  NR_HIP(ctx, hipSetDevice(ctx->device));
-  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  reset_dataset(ctx);
-  ctx->cancel = false;  // a context cancelled after its run returned starts clean
-  return NR_OK;
-}
+extern "C" {
 
 // The per-batch work buffers (the column sweep's sets, the profile slots'
 // scratch, the device output and shuffle-table buffers); the next run
@@ -1993,33 +1144,6 @@ int nr_debug_set(int what, int64_t value) {
   }
 }
 
-int nr_dataset_symmetric(nr_ctx* ctx, int* symmetric) {
-  if (!ctx || !symmetric) return NR_ERR_INVALID;
-  if (!ctx->d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
-  *symmetric = ctx->symmetric;
-  return NR_OK;
-}
-
-int nr_gram_table(nr_ctx* ctx, int* on) {
-  if (!ctx || !on) return NR_ERR_INVALID;
-  *on = ctx->d_pairs && ctx->pairs_es == 2 ? 1 : 0;
-  return NR_OK;
-}
-
-int nr_gram_table_ms(nr_ctx* ctx, double* ms) {
-  if (!ctx || !ms) return NR_ERR_INVALID;
-  *ms = ctx->d_pairs && ctx->pairs_es == 2 ? ctx->table_ms : 0.0;
-  return NR_OK;
-}
-
-int nr_dataset_finite(nr_ctx* ctx, int* corr_finite, int* net_finite) {
-  if (!ctx || !corr_finite || !net_finite) return NR_ERR_INVALID;
-  if (!ctx->d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
-  *corr_finite = ctx->corr_finite;
-  *net_finite = ctx->net_finite;
-  return NR_OK;
-}
-
 int nr_set_modules(nr_ctx* ctx, int32_t n_rows, int32_t n_present, const int32_t* row_of,
                    const int64_t* node_off, const int32_t* test_idx, const int32_t* null_pos,
                    const double* disc_corr, const double* disc_degree, const double* disc_contrib) {
@@ -2064,7 +1188,7 @@ int nr_set_modules(nr_ctx* ctx, int32_t n_rows, int32_t n_present, const int32_t
       break;
     }
   for (int64_t i = 0; i < ctx->n_node_total; ++i)
-    if (test_idx[i] < 0 || test_idx[i] >= ctx->n_nodes)
+    if (test_idx[i] < 0 || test_idx[i] >= ctx->ds.n_nodes)
       return fail(ctx, NR_ERR_INVALID, "test_idx outside the resident dataset (call nr_set_dataset first)");
   ctx->null_pos_max = -1;
   if (null_pos) {
@@ -2092,7 +1216,7 @@ int nr_set_modules(nr_ctx* ctx, int32_t n_rows, int32_t n_present, const int32_t
   ctx->order_k_h.resize(n_present);
   for (int i = 0; i < n_present; ++i) ctx->order_k_h[i] = (int32_t)(node_off[order[i] + 1] - node_off[order[i]]);
   NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->d_data && !ctx->d_disc_nc && n_present > 0)
+  if (ctx->ds.d_data && !ctx->d_disc_nc && n_present > 0)
     return fail(ctx, NR_ERR_INVALID, "dataset has data but disc_contrib is NULL");
   ctx->modules_gen = ctx->data_gen;
   return NR_OK;
@@ -2103,7 +1227,7 @@ int nr_set_null_pool(nr_ctx* ctx, const int32_t* null_idx, int64_t n_null) {
   if (!null_idx || n_null <= 0 || n_null > (int64_t)UINT32_MAX / 4)
     return fail(ctx, NR_ERR_INVALID, "bad null pool");
   for (int64_t i = 0; i < n_null; ++i)
-    if (null_idx[i] < 0 || null_idx[i] >= ctx->n_nodes)
+    if (null_idx[i] < 0 || null_idx[i] >= ctx->ds.n_nodes)
       return fail(ctx, NR_ERR_INVALID, "null_idx outside the resident dataset");
   NR_HIP(ctx, hipSetDevice(ctx->device));
   NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2207,8 +1331,8 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
                       double* corr_vec, double* degree, double* avg_weight, double* contribution,
                       double* summary, double* coherence) {
   if (!ctx || n_mod < 0 || (n_mod > 0 && (!node_off || !idx))) return NR_ERR_INVALID;
-  if (!ctx->d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
-  if ((contribution || summary || coherence) && !ctx->d_data)
+  if (!ctx->ds.d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
+  if ((contribution || summary || coherence) && !ctx->ds.d_data)
     return fail(ctx, NR_ERR_INVALID, "contribution/summary need a dataset with data");
   if (n_mod == 0) return NR_OK;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2223,7 +1347,7 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
   }
   const int64_t nodes = node_off[n_mod];
   for (int64_t i = 0; i < nodes; ++i)
-    if (idx[i] < 0 || idx[i] >= ctx->n_nodes) return fail(ctx, NR_ERR_INVALID, "idx outside the dataset");
+    if (idx[i] < 0 || idx[i] >= ctx->ds.n_nodes) return fail(ctx, NR_ERR_INVALID, "idx outside the dataset");
   std::vector<int32_t> order(n_mod);
   for (int m = 0; m < n_mod; ++m) order[m] = m;
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
@@ -2238,7 +1362,7 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
     dfree(d_off); dfree(d_cv); dfree(d_idx); dfree(d_order);
     dfree(d_cvo); dfree(d_wd); dfree(d_nc); dfree(d_sp); dfree(d_coh); dfree(d_aw);
   };
-  const int64_t S = ctx->n_samples;
+  const int64_t S = ctx->ds.n_samples;
   do {
     if ((rc = upload(ctx, d_off, node_off, (size_t)n_mod + 1))) break;
     if ((rc = upload(ctx, d_cv, cv.data(), cv.size()))) break;
@@ -2247,17 +1371,17 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
     hipError_t e = hipMalloc((void**)&d_cvo, (size_t)std::max<int64_t>(cv.back(), 1) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&d_wd, (size_t)nodes * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&d_aw, (size_t)n_mod * sizeof(double));
-    if (e == hipSuccess && ctx->d_data) e = hipMalloc((void**)&d_nc, (size_t)nodes * sizeof(double));
-    if (e == hipSuccess && ctx->d_data) e = hipMalloc((void**)&d_sp, (size_t)(n_mod * S) * sizeof(double));
-    if (e == hipSuccess && ctx->d_data) e = hipMalloc((void**)&d_coh, (size_t)n_mod * sizeof(double));
+    if (e == hipSuccess && ctx->ds.d_data) e = hipMalloc((void**)&d_nc, (size_t)nodes * sizeof(double));
+    if (e == hipSuccess && ctx->ds.d_data) e = hipMalloc((void**)&d_sp, (size_t)(n_mod * S) * sizeof(double));
+    if (e == hipSuccess && ctx->ds.d_data) e = hipMalloc((void**)&d_coh, (size_t)n_mod * sizeof(double));
     if (e != hipSuccess) { rc = hip_fail(ctx, e, "hipMalloc module vectors"); break; }
     nr::IndexSource src = make_source(ctx, nr::NR_IDX_DIRECT, 0, 0, nullptr, d_idx);
     nr::NetParams np{};
-    np.pairs = ctx->d_pairs;
-    np.es = ctx->pairs_es;
-    np.colsum = ctx->d_colsum;
-    np.n_nodes = ctx->n_nodes;
-    np.symmetric = ctx->symmetric;
+    np.pairs = ctx->ds.d_pairs;
+    np.es = ctx->ds.pairs_es;
+    np.colsum = ctx->ds.d_colsum;
+    np.n_nodes = ctx->ds.n_nodes;
+    np.symmetric = ctx->ds.symmetric;
     np.src = src;
     np.node_off = d_off;
     np.cv_off = d_cv;
@@ -2271,11 +1395,11 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
     for (int i = 0; i < n_mod; ++i) k_sorted[i] = (int32_t)(node_off[order[i] + 1] - node_off[order[i]]);
     if ((rc = launch_nets(ctx, np, d_order, k_sorted, 1, main_lane(ctx)))) break;
     e = hipSuccess;
-    if (ctx->d_data && (contribution || summary || coherence)) {
+    if (ctx->ds.d_data && (contribution || summary || coherence)) {
       nr::ProfileParams pp{};
-      pp.data = ctx->d_data;
+      pp.data = ctx->ds.d_data;
       pp.n_samples = S;
-      pp.ones_off = ctx->n_nodes * S;
+      pp.ones_off = ctx->ds.n_nodes * S;
       pp.src = src;
       pp.node_off = d_off;
       pp.n_perm = 1;
@@ -2466,9 +1590,6 @@ int nr_synchronize(nr_ctx* ctx) {
   return NR_OK;
 }
 
-}  // extern "C"
-
-extern "C" {
 // Host evaluation of the keyed null-pool permutation (prp.h) for tests and
 // for callers that want to export the exact shuffles a run uses.
 int nr_prp_table(uint64_t seed, int64_t perm_begin, int64_t perm_end, int64_t n_null,

@@ -117,7 +117,8 @@ class Engine:
 
     def netbuild_ms(self) -> float:
         """Device time in ms of the from-data build of the resident matrices
-        (nr_netbuild_ms), 0 for a dataset made any other way."""
+        (nr_netbuild_ms), 0 for a dataset made any other way. A copy reports
+        the figure of the dataset it was copied from."""
         ms = C.c_double()
         self._check(self._lib.nr_netbuild_ms(self._h, C.byref(ms)))
         return float(ms.value)
@@ -131,16 +132,18 @@ class Engine:
         self._check(self._lib.nr_set_dataset_files(self._h, enc(corr_path), enc(net_path), enc(data_path),
                                                    enc(objects[0]), enc(objects[1]), enc(objects[2]),
                                                    int(bool(scale_data))))
-        n, s_ = C.c_int64(), C.c_int64()
-        self._check(self._lib.nr_dataset_shape(self._h, C.byref(n), C.byref(s_)))
+        self.n_stat = 7 if data_path is not None else 4
+        self.n_nodes, self.n_samples = self.shape()
+        return self.colnames()
+
+    def colnames(self):
+        """Column names of the resident dataset (nr_dataset_colnames): those of
+        the files it was loaded from, carried by its copies; [] otherwise."""
         need = C.c_int64()
         self._check(self._lib.nr_dataset_colnames(self._h, None, 0, C.byref(need)))
         buf = C.create_string_buffer(max(need.value, 1))
         self._check(self._lib.nr_dataset_colnames(self._h, buf, need.value, C.byref(need)))
         names = buf.raw[:need.value].split(b"\0")[:-1] if need.value else []
-        self.n_stat = 7 if data_path is not None else 4
-        self.n_nodes = n.value
-        self.n_samples = s_.value
         return [x.decode() for x in names]
 
     def set_dataset_device(self, corr_ptr: int, net_ptr: int, data_ptr, n_nodes: int, n_samples: int):

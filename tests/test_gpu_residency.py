@@ -282,3 +282,124 @@ def test_broadcast_across_two_physical_devices_bitwise():
             e.set_null_pool(mi.null_idx)
             outs.append(e.run(0, 32, seed=9))
         _same_arr(outs[0], outs[1])
+
+
+# --------------------------------------------------------------------------
+# one Dataset value per context: what a copy carries, what a rejected call
+# keeps, and the staging loop behind every host upload
+# --------------------------------------------------------------------------
+
+def _load_modules(e, mi, disc):
+    mods = mi.mods_present
+    node_off = np.concatenate([[0], np.cumsum([mi.test_idx[m].size for m in mods])])
+    e.set_modules(len(mi.modules), [mi.modules.index(m) for m in mods], node_off,
+                  np.concatenate([mi.test_idx[m] for m in mods]),
+                  np.concatenate([mi.null_pos[m] for m in mods]),
+                  np.concatenate([disc["corr"][m] for m in mods]),
+                  np.concatenate([disc["degree"][m] for m in mods]),
+                  np.concatenate([disc["contribution"][m] for m in mods]))
+    e.set_null_pool(mi.null_idx)
+
+
+def _copies_of(src, engines):
+    """engines[0] by nr_copy_dataset, the rest by one nr_broadcast_dataset."""
+    engines[0].copy_dataset_from(src)
+    src.broadcast_dataset_to(engines[1:])
+    return engines
+
+
+def test_copies_carry_every_field_with_the_gram_table():
+    """A dataset that holds the Gram table, copied (nr_copy_dataset) and
+    broadcast: every copy has the table and its build time
+    (include/netrep_gpu.h: 0 means "no table"), the shape and the flags of the
+    source, and runs bitwise like it."""
+    from test_gpu_dual import _case
+    lay, mi, disc, txs, tc, tn = _case([150, 60, 33], 160, 41, n_nodes=500)
+    engines = [N.Engine(0) for _ in range(4)]
+    try:
+        src = engines[0]
+        src.set_dataset(tc, tn, txs)
+        _load_modules(src, mi, disc)
+        ref = src.run(0, 4, 7)               # builds the table
+        assert src.gram_table() and src.gram_table_ms() > 0
+        for e in _copies_of(src, engines[1:]):
+            assert e.gram_table()
+            assert e.gram_table_ms() == src.gram_table_ms()
+            assert e.shape() == src.shape() == (500, 160)
+            assert e.symmetric() == src.symmetric()
+            assert e.finite() == src.finite()
+            _load_modules(e, mi, disc)
+            _same_arr(ref, e.run(0, 4, 7))
+    finally:
+        for e in engines:
+            e.close()
+
+
+def test_copies_carry_names_and_the_from_data_time(tmp_path, bundled):
+    """The column names of a dataset loaded from files, and the build time of
+    one made from its data matrix, are the source's on a copy and on a
+    broadcast copy."""
+    from rds_writer import write_rds
+    b = bundled
+    pc, pn = str(tmp_path / "c.rds"), str(tmp_path / "n.rds")
+    write_rds(pc, b["test_correlation"], None, list(b["test_correlation_colnames"]))
+    write_rds(pn, b["test_network"], None, list(b["test_network_colnames"]))
+    n, s = 600, 40
+    x = np.random.default_rng(5).normal(size=(s, n))
+    engines = [N.Engine(0) for _ in range(3)]
+    try:
+        src = engines[0]
+        names = src.set_dataset_files(pc, pn)
+        assert names == list(b["test_network_colnames"])
+        for e in _copies_of(src, engines[1:]):
+            assert e.colnames() == names
+            assert e.netbuild_ms() == 0
+        src.set_dataset_from_data(x, 5.0)
+        assert src.netbuild_ms() > 0
+        for e in _copies_of(src, engines[1:]):
+            assert e.netbuild_ms() == src.netbuild_ms()
+            assert e.shape() == (n, s)
+            assert e.colnames() == []
+    finally:
+        for e in engines:
+            e.close()
+
+
+def test_rejected_set_dataset_keeps_the_old_dataset():
+    """A call rejected for its arguments (an unknown nr_set_dataset_ex flag
+    bit, beta = 0) returns NR_ERR_INVALID before anything is replaced: shape,
+    modules and null pool stay, and the same run is bitwise the first."""
+    from netrep_amd import _lib as L
+    from netrep_amd.engine import _ptr
+    lay, names, ma, x, c, nt = _dataset(n=800, s=40, seed=51, sizes=(60, 30))
+    node_off, idx = S.csr_of(lay)
+    k = node_off[1:] - node_off[:-1]
+    dcv, dwd = np.zeros(int((k * (k - 1) // 2).sum())), np.zeros(int(k.sum()))
+    with N.Engine(0) as eng:
+        eng.set_dataset(c, nt, None)
+        eng.set_modules(len(k), np.arange(len(k), dtype=np.int32), node_off, idx, idx, dcv, dwd)
+        eng.set_null_pool(np.arange(len(names), dtype=np.int32))
+        first = eng.run(0, 8, seed=3)
+        rc = eng._lib.nr_set_dataset_ex(eng._h, _ptr(c), _ptr(nt), None, c.shape[0], 0, L.NR_HOST, 2)
+        assert rc == L.NR_ERR_INVALID
+        with pytest.raises(N.NetRepError) as ei:
+            eng.set_dataset_from_data(x, beta=0.0)
+        assert ei.value.code == L.NR_ERR_INVALID
+        assert eng.shape() == (800, 0)
+        _same_arr(first, eng.run(0, 8, seed=3))
+
+
+def test_host_upload_across_staging_buffer_reuse():
+    """n = 4,100: 16.81 M elements per matrix, three 2^23-element chunks with a
+    short last one, so each pinned buffer is waited for and filled a second
+    time. Both matrices come back bitwise, and exactly their bytes crossed."""
+    n = 4100
+    rng = np.random.default_rng(17)
+    c, nt = rng.random((n, n)).T, rng.random((n, n)).T      # column-major, no copy on the way in
+    with N.Engine(0) as eng:
+        before = N.h2d_bytes()
+        eng.set_dataset(c, nt, None)
+        assert N.h2d_bytes() - before == 16 * n * n
+        gc, gn = eng.matrices()
+    _same_arr(gc, c)
+    _same_arr(gn, nt)
