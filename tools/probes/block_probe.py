@@ -1,6 +1,6 @@
 """Driver of tools/probes/block_probe.hip: block Lanczos
-b = 16 on the matrix cores for C3-shaped null items (the eig_probe.py items:
-20k genes x 500 samples, sizes round(linspace(30, 300, 50))).
+b = 16 on the matrix cores for C3-shaped null items (20k genes x 500
+samples, sizes round(linspace(30, 300, 50))).
 
 Per real item the host runs the offline study's block Lanczos (full
 reorthogonalisation, Rayleigh-Ritz, stop at |G v - theta v| <= 5e-15 theta)

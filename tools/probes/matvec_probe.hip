@@ -10,6 +10,7 @@
 //   /tmp/matvec_probe [k] [passes] [LDS KiB per workgroup: 52 -> 3 per CU, 80 -> 2, 160 -> 1]
 #include "../../netrep_amd/csrc/kernels.hip"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -447,6 +448,7 @@ __device__ __forceinline__ double chunked_matvec(const double* __restrict__ Ga, 
 template <int V>
 __global__ void __launch_bounds__(256, 3) mv_probe(double* Gall, int64_t stride, int k, int passes, double* res, int64_t ga_off) {
   const int64_t ch_off = ga_off + (ga_total(k + 1) + 31) / 32 * 32;
+  const int64_t pk_off = ch_off + (ga_total(k + 1) + 31) / 32 * 32;  // the product's layout
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int NW = 4, KS = 320;
   double* red = reinterpret_cast<double*>(smem);
@@ -472,7 +474,7 @@ __global__ void __launch_bounds__(256, 3) mv_probe(double* Gall, int64_t stride,
       for (int c = threadIdx.x; c < k; c += 256) w[c] = x[c];
       __syncthreads();
     } else {
-      lam = V == 0 ? packed_matvec<NW>(G, k + 1, k, x, w, part, KS, x, red)
+      lam = V == 0 ? packed_matvec<NW, false, false, true>(G + pk_off, k + 1, k, x, w, part, KS, x, red)
                    : packed_matvec_pipe<NW>(G, k + 1, k, x, w, part, upper, KS, x, red);
     }
     const double inv = 1.0 / fabs(lam);
@@ -492,14 +494,10 @@ int main(int argc, char** argv) {
   const int slots = 3 * cu;
   const int kc = k + 1;
   const int64_t tri = (int64_t)kc * (kc + 1) / 2 + 1;
-  const int64_t stride = 3 * ((tri + 31) / 32 * 32 + 4096);  // three layouts of the Gram
   std::vector<double> h(tri);
   srand(7);
   for (int64_t i = 0; i < tri; ++i) h[i] = (double)rand() / RAND_MAX;
   h[tri - 1] = 0.0;
-  double *G, *res;
-  (void)hipMalloc(&G, stride * slots * sizeof(double));
-  (void)hipMalloc(&res, slots * sizeof(double));
   // the same matrix in the group-aligned layout, behind the packed one in each slot
   const int P = nr::ga_pad(kc);
   std::vector<double> ha(nr::ga_total(kc), 0.0);
@@ -516,7 +514,26 @@ int main(int argc, char** argv) {
     const int64_t pcol = (int64_t)c * kc - (int64_t)c * (c - 1) / 2;
     for (int r = c; r < kc; ++r) hc[nr::ch_at(r, c, P)] = h[pcol + r - c];
   }
+  // and in the product's layout (kernels.hip packed_gram_doubles: the chunked
+  // groups without row padding, the node columns' diagonal entries halved)
+  const int64_t pk_off = ch_off + (hc.size() + 31) / 32 * 32;
+  std::vector<double> hp(nr::packed_gram_doubles(kc), 0.0);
+  for (int c = 0; c < kc; ++c) {
+    const int64_t pcol = (int64_t)c * kc - (int64_t)c * (c - 1) / 2;
+    const int g = c >> 4;
+    for (int r = c; r < kc; ++r) {
+      const int rr = r - 16 * g, j = rr >> 6;
+      const int hh = std::min(64, kc - 16 * g - 64 * j);
+      const double v = h[pcol + r - c];
+      hp[nr::pk_base(g, kc) + 1024 * (int64_t)j + (int64_t)(c & 15) * hh + (rr & 63)] = (r == c && c < k) ? 0.5 * v : v;
+    }
+  }
+  const int64_t stride = pk_off + (int64_t)hp.size() + 4096;  // four layouts of the Gram
+  double *G, *res;
+  (void)hipMalloc(&G, stride * slots * sizeof(double));
+  (void)hipMalloc(&res, slots * sizeof(double));
   for (int s = 0; s < slots; ++s) {
+    (void)hipMemcpy(G + (int64_t)s * stride + pk_off, hp.data(), hp.size() * sizeof(double), hipMemcpyHostToDevice);
     (void)hipMemcpy(G + (int64_t)s * stride, h.data(), tri * sizeof(double), hipMemcpyHostToDevice);
     (void)hipMemcpy(G + (int64_t)s * stride + ga_off, ha.data(), ha.size() * sizeof(double), hipMemcpyHostToDevice);
     (void)hipMemcpy(G + (int64_t)s * stride + ch_off, hc.data(), hc.size() * sizeof(double), hipMemcpyHostToDevice);
