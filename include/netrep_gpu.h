@@ -307,12 +307,23 @@ int nr_scratch_bytes(const nr_ctx* ctx, int64_t* bytes);
 /* A context's own host-thread count (nr_ctx_set_host_threads). */
 int nr_ctx_get_host_threads(const nr_ctx* ctx, int* n);
 
-/* Test knobs, process-wide; neither changes a result. NR_DEBUG_SWEEP_MAX_OCC:
- * the column sweep's sub-batch bound in occurrences (value <= 0 restores the
- * default, 64M). NR_DEBUG_FAIL_SWEEP_ALLOC: the value-th column-sweep buffer
- * allocation from now fails with NR_ERR_OOM (0: off). */
+/* Test knobs, process-wide. The first two change no result.
+ * NR_DEBUG_SWEEP_MAX_OCC: the column sweep's sub-batch bound in occurrences
+ * (value <= 0 restores the default, 64M). NR_DEBUG_FAIL_SWEEP_ALLOC: the
+ * value-th column-sweep buffer allocation from now fails with NR_ERR_OOM (0:
+ * off). NR_DEBUG_SWEEP_CHUNK_ROWS: a positive multiple of 64 caps the rows per
+ * column chunk of the sweep in place of the LDS budget's cap (9,984 rows of
+ * {corr, net}); the chunks stay balanced and rounded to 64 rows, a value above
+ * the budget's cap has no effect, value <= 0 restores the default, any other
+ * value returns NR_ERR_INVALID. It regroups the CorrVector partial sums, so
+ * cor.cor and avg.cor move at rounding level; avg.weight and cor.degree (exact
+ * fixed-point parts, or plain sums cut at other places) move at rounding
+ * level at most. Whether the sweep runs at all is decided from the production
+ * height; a cap that gives more than 16 chunks makes the run fail with
+ * NR_ERR_INVALID instead of taking another kernel. */
 #define NR_DEBUG_SWEEP_MAX_OCC 1
 #define NR_DEBUG_FAIL_SWEEP_ALLOC 2
+#define NR_DEBUG_SWEEP_CHUNK_ROWS 3
 int nr_debug_set(int what, int64_t value);
 
 /* ---- reference-interface layer ----------------------------------------- */

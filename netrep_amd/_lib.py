@@ -145,6 +145,7 @@ SIGNATURES = {
 }
 NR_DEBUG_SWEEP_MAX_OCC = 1
 NR_DEBUG_FAIL_SWEEP_ALLOC = 2
+NR_DEBUG_SWEEP_CHUNK_ROWS = 3
 
 _lib = None
 

@@ -417,20 +417,25 @@ int launch_nets(nr_ctx* ctx, nr::NetParams np, const int32_t* d_order, const std
 // occurrence ids, bounded buffers); an item's statistics do not depend on
 // the batch it runs in, so neither do the results.
 constexpr int64_t kSweepMaxOcc = (int64_t)64 << 20;
-// nr_debug_set test knobs (neither changes a result): a smaller sub-batch
-// bound, and an injected failure of the n-th sweep buffer allocation.
+// nr_debug_set test knobs: a smaller sub-batch bound and an injected failure
+// of the n-th sweep buffer allocation (neither changes a result), and a lower
+// cap on the rows per column chunk (0: the production cap), which regroups the
+// CorrVector partial sums (cor.cor and avg.cor move at rounding level). The
+// choice of the sweep (sweep_supported) never depends on the last.
 std::atomic<int64_t> g_sweep_max_occ{kSweepMaxOcc};
 std::atomic<int> g_fail_sweep_alloc{0};
+std::atomic<int64_t> g_sweep_chunk_rows{0};
 constexpr int64_t kSweepMaxRecBytes = (int64_t)32 << 30;  // the (occurrence, chunk) records of one sub-batch
 
-int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const Lane& ln);
+int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, int64_t chunk_rows, const Lane& ln);
 
 int launch_sweep_batch(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const Lane& ln) {
   // occurrences per sub-batch: at most kSweepMaxOcc, and records of at most
   // kSweepMaxRecBytes (many column chunks at large n)
-  const int64_t chunks =
-      (ctx->ds.n_nodes + nr::sweep_chunk_rows(ctx->ds.n_nodes, np.disc_cv ? 16 : 8) - 1) /
-      nr::sweep_chunk_rows(ctx->ds.n_nodes, np.disc_cv ? 16 : 8);
+  const int64_t chunk_rows = nr::sweep_chunk_rows(ctx->ds.n_nodes, np.disc_cv ? 16 : 8, g_sweep_chunk_rows.load());
+  const int64_t chunks = (ctx->ds.n_nodes + chunk_rows - 1) / chunk_rows;
+  if (chunks > nr::kSweepMaxChunks)  // only the test knob gets here (sweep_supported: the production height)
+    return fail(ctx, NR_ERR_INVALID, "NR_DEBUG_SWEEP_CHUNK_ROWS gives more column chunks than the sweep holds (16)");
   const int64_t max_occ = std::min<int64_t>(g_sweep_max_occ.load(), kSweepMaxRecBytes / (chunks * 8 * nr::kSweepRec));
   const int64_t per = std::max<int64_t>(1, max_occ / std::max<int64_t>(ctx->n_node_total, 1));
   for (int64_t p0 = 0; p0 < n_perm; p0 += per) {
@@ -439,16 +444,16 @@ int launch_sweep_batch(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, con
     q.src.perm_base = np.src.perm_base + p0;
     if (q.src.mode == nr::NR_IDX_TABLE) q.src.pi = np.src.pi + p0 * (int64_t)np.src.n_null;
     q.out = np.out + p0 * (int64_t)np.n_rows * np.n_stat;
-    if (int rc = launch_sweep_sub(ctx, q, np_sub, ln)) return rc;
+    if (int rc = launch_sweep_sub(ctx, q, np_sub, chunk_rows, ln)) return rc;
   }
   return NR_OK;
 }
 
-int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, const Lane& ln) {
+int launch_sweep_sub(nr_ctx* ctx, const nr::NetParams& np, int64_t n_perm, int64_t chunk_rows, const Lane& ln) {
   nr_ctx::SweepBuf& b = ctx->sweep[ln.id];
   const size_t n_occ = (size_t)(n_perm * ctx->n_node_total);
   nr::SweepParams P{};
-  P.chunk_rows = nr::sweep_chunk_rows(ctx->ds.n_nodes, np.disc_cv ? 16 : 8);
+  P.chunk_rows = chunk_rows;
   P.n_chunks = (int32_t)((ctx->ds.n_nodes + P.chunk_rows - 1) / P.chunk_rows);
   // Every buffer of a set is freed before it is reallocated, so a set's
   // capacity is committed only once the whole chain has succeeded: after an
@@ -1138,6 +1143,10 @@ int nr_debug_set(int what, int64_t value) {
       return NR_OK;
     case NR_DEBUG_FAIL_SWEEP_ALLOC:
       g_fail_sweep_alloc = (int)std::max<int64_t>(0, value);
+      return NR_OK;
+    case NR_DEBUG_SWEEP_CHUNK_ROWS:
+      if (value > 0 && value % 64 != 0) return NR_ERR_INVALID;
+      g_sweep_chunk_rows = value > 0 ? value : 0;
       return NR_OK;
     default:
       return NR_ERR_INVALID;

@@ -167,7 +167,7 @@ struct SweepParams {
   double* out;
 };
 // rows per chunk for LDS elements of elem_bytes (16: {corr, net}; 8: net only)
-int64_t sweep_chunk_rows(int64_t n_nodes, int elem_bytes);
+int64_t sweep_chunk_rows(int64_t n_nodes, int elem_bytes, int64_t cap_rows = 0);
 bool sweep_supported(int64_t n_nodes, int k_max);
 hipError_t launch_sweep(const SweepParams& P, hipStream_t st);
 

@@ -685,10 +685,12 @@ bool sweep_supported(int64_t n_nodes, int k_max) {
          (n_nodes + sweep_chunk_rows(n_nodes, 16) - 1) / sweep_chunk_rows(n_nodes, 16) <= kSweepMaxChunks;
 }
 
-int64_t sweep_chunk_rows(int64_t n_nodes, int elem_bytes) {
+int64_t sweep_chunk_rows(int64_t n_nodes, int elem_bytes, int64_t cap_rows) {
   // chunks of at most kSweepChunkBytes of LDS, balanced, whole 64-row groups
-  // (within the budget: the cap is a multiple of 64 rows)
-  const int64_t cap = kSweepChunkBytes / elem_bytes / 64 * 64;
+  // (within the budget: the cap is a multiple of 64 rows). cap_rows > 0 (a
+  // multiple of 64: nr_debug_set's test knob) lowers the cap.
+  const int64_t lds_cap = kSweepChunkBytes / elem_bytes / 64 * 64;
+  const int64_t cap = cap_rows > 0 ? std::min(cap_rows, lds_cap) : lds_cap;
   const int64_t n_chunks = (n_nodes + cap - 1) / cap;
   const int64_t rows = (n_nodes + n_chunks - 1) / n_chunks;
   return std::min(cap, (rows + 63) / 64 * 64);
