@@ -711,6 +711,26 @@ __device__ __forceinline__ double rg_row_reduce(const double (&a)[4], int lane) 
 }
 
 // ---------------------------------------------------------------------------
+// Sizes the launch planner (profile_plan.hip) shares with the kernels.
+// ---------------------------------------------------------------------------
+
+// The network item's per-node arrays (NetLds, carve_net_lds in kernels.hip):
+// their padded stride, and the bytes of the whole carve-out.
+__host__ __device__ __forceinline__ int net_kpad(int kmax) { return kmax + (kmax >> 5) + 1; }
+inline size_t net_lds_bytes(int nw, int kmax) {
+  const size_t kp = (size_t)net_kpad(kmax);
+  return sizeof(double) * (8 * (size_t)nw + (size_t)(nw + 2) * kp) + sizeof(unsigned long long) * 3 * kp +
+         sizeof(int) * ((size_t)kmax + 2 * kp);
+}
+
+// The packed symmetric Gram's column groups and where group g of a side-P
+// Gram starts (layout described at pk_store_tile, kernels.hip).
+__host__ __device__ __forceinline__ int pk_groups(int kc) { return (kc + 15) >> 4; }
+__host__ __device__ __forceinline__ int64_t pk_base(int g, int P) {
+  return 16 * (int64_t)g * P - 128 * (int64_t)g * (g - 1);
+}
+
+// ---------------------------------------------------------------------------
 // Summary-profile item pipeline pieces shared by every Gram storage scheme:
 // LDS carve-out, node contributions from the Ritz vector, the statistics, and
 // the persistent work queue.
@@ -731,12 +751,21 @@ struct LzLds {
   int mmax;
 };
 
+// Bytes carve_lds<nw> carves, up to the end of idx (profile_plan_check.hip
+// holds the two against each other).
+__host__ __device__ __forceinline__ size_t carve_lds_bytes(int nw, int kvec, int mmax, int64_t extra,
+                                                           bool twork_in_extra) {
+  return sizeof(double) * (8 * (size_t)nw + 6 * (size_t)kvec + (size_t)extra +
+                           (twork_in_extra ? 4 : 9) * (size_t)mmax + 3 * ((size_t)mmax + 1)) +
+         sizeof(uint32_t) * (size_t)kvec;
+}
+
 // Carves red, q, qprev, w, vv, gv, colm (kvec each), then `extra` doubles for
 // the storage scheme (returned in *extra_out), then the Lanczos tridiagonal
-// arrays and idx. Layout matches profile_kernel_lds.
+// arrays and idx: carve_lds_bytes in all.
 template <int NW>
-__device__ __forceinline__ LzLds carve_lds(unsigned char* smem, int kvec, int mmax, int64_t extra,
-                                           double** extra_out, bool twork_in_extra = false) {
+__host__ __device__ __forceinline__ LzLds carve_lds(unsigned char* smem, int kvec, int mmax, int64_t extra,
+                                                    double** extra_out, bool twork_in_extra = false) {
   LzLds L;
   L.red = reinterpret_cast<double*>(smem);  // 8 * NW
   L.q = L.red + 8 * NW;
@@ -759,13 +788,22 @@ __device__ __forceinline__ LzLds carve_lds(unsigned char* smem, int kvec, int mm
   return L;
 }
 
-// Variant 6 (Lanczos dimensions beyond the LDS vectors): only the reduction
-// scratch and the tridiagonal arrays in LDS; the six vectors (kvec each) and
-// the index set in the slot's global scratch at `gvec` (the workgroup's
-// barriers order them: one CU, one vector L1). Same roles as carve_lds with
-// twork outside the partials.
+// What carve_split<nw> carves: bytes of LDS, and doubles of the slot's scratch
+// from gvec on (the index set's kvec words rounded up to doubles).
+__host__ __device__ __forceinline__ size_t carve_split_bytes(int nw, int mmax) {
+  return sizeof(double) * (8 * (size_t)nw + 9 * (size_t)mmax + 3 * ((size_t)mmax + 1));
+}
+__host__ __device__ __forceinline__ int64_t carve_split_doubles(int kvec) {
+  return 6 * (int64_t)kvec + (kvec + 1) / 2;
+}
+
+// ProfileClass::FullVectorsInScratch (Lanczos dimensions beyond the LDS
+// vectors): only the reduction scratch and the tridiagonal arrays in LDS; the
+// six vectors (kvec each) and the index set in the slot's global scratch at
+// `gvec` (the workgroup's barriers order them: one CU, one vector L1). Same
+// roles as carve_lds with twork outside the partials.
 template <int NW>
-__device__ __forceinline__ LzLds carve_split(unsigned char* smem, double* gvec, int kvec, int mmax) {
+__host__ __device__ __forceinline__ LzLds carve_split(unsigned char* smem, double* gvec, int kvec, int mmax) {
   LzLds L;
   L.red = reinterpret_cast<double*>(smem);  // 8 * NW
   L.alpha = L.red + 8 * NW;

@@ -58,40 +58,6 @@ int fill_na(nr_ctx* ctx, double* d, int64_t n, hipStream_t st = nullptr) {
 
 int n_stat_of(const nr_ctx* ctx) { return ctx->ds.d_data ? NR_NSTAT_DATA : NR_NSTAT_NODATA; }
 
-// Lanczos basis columns per item: 160 covers every C2/C3 module (<= 46 steps
-// measured); large modules (C5: up to 2,000 nodes, spectra with small gaps)
-// get 320.
-int profile_m_max(int k_max) { return k_max <= 320 ? std::min(k_max, 160) : 320; }
-// Leading dimension of the per-slot Gram: k module columns + the ones column,
-// padded to a 32-column super-tile.
-int gram_ld(int k_max) { return (k_max + 1 + 31) / 32 * 32; }
-
-// Launch plan of one summary-profile launch (one size class of modules):
-//   variant 2: the packed symmetric Gram in global scratch, 4-wave
-//              workgroups, 3 per CU (module_profile_packed4_kernel; the
-//              compile-time LDS layout of 320-node modules, or a runtime one);
-//   variant 0: the full Gram, where the packed layout's LDS does not fit;
-//   variant 4: the full Gram with the matvec partials in scratch, where even
-//              that does not fit; `big`: the per-node arrays in scratch too
-//              (modules beyond the LDS vectors; dual Gram only);
-//   variant 6: variant 4 with every Lanczos vector and the index set in
-//              scratch (Lanczos dimension min(k, S) beyond the LDS vectors).
-// Modules with k > S use the S x S dual Gram. One numerical path per layout:
-// no run-time switch selects another (round-2 A/B variants are compile-time
-// history, profiles/r02/profile_variants.txt and profiles/r03/).
-struct ProfilePlan {
-  int variant = 0;
-  int slots = 0;
-  int per_cu = 1;
-  int64_t gram_doubles = 0, stride = 0;
-  int k_gram = 0;     // side of the largest Gram (minus the ones column)
-  int m = 0;          // Lanczos basis columns
-  int kvec = 0;       // LDS vector length
-  bool big = false;   // modules beyond kvec (per-node arrays in scratch)
-  int64_t basis_doubles = 0;
-  int64_t g32_off = 0;  // fp32 Gram copy (relaxed Lanczos steps), 0: none
-};
-
 // Queue order of the summary-profile items. Module-major (every permutation
 // of the largest module, then the next: largest-first scheduling) balances
 // the slots best, but keeps the largest Grams in flight together: at C3 the
@@ -129,112 +95,12 @@ int profile_order_tail(int slots, const std::vector<int32_t>& k_sorted, int firs
   return (top > budget && mix <= budget) ? (int)t : 0;
 }
 
-int plan_profile(nr_ctx* ctx, int64_t n_items, int k_max, int n_samples, ProfilePlan* plan, int64_t data_doubles) {
+// nr::plan_profile (profile_plan.h) for the context's device.
+int plan_profile(nr_ctx* ctx, int64_t n_items, int k_max, int n_samples, nr::ProfilePlan* plan, int64_t data_doubles) {
   int dev_cu = 256;
   (void)hipDeviceGetAttribute(&dev_cu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-  int variant = 2;
-  // the dual (S x S) Gram of modules with k > S: the Gram side is min(k, S),
-  // and so is every Lanczos dimension (basis columns of that length)
-  plan->k_gram = std::min(k_max, n_samples);
-  // (its buffer loads take 32-bit byte offsets into the data block)
-  if (plan->k_gram <= nr::kWaveDim && data_doubles * 8 < ((int64_t)1 << 31)) {
-    // the wave class (kernels.h): one wave per item, the Gram in its
-    // registers; the slot's scratch holds the Lanczos basis, and the per-node
-    // arrays of modules longer than the LDS vectors
-    plan->variant = 7;
-    plan->m = nr::kWaveVec;
-    plan->kvec = nr::kWaveVec;
-    plan->big = k_max > nr::kWaveVec;
-    plan->per_cu = nr::profile_wave_per_cu();
-    plan->slots = (int)std::max<int64_t>(1, std::min<int64_t>(n_items, (int64_t)dev_cu * plan->per_cu));
-    plan->gram_doubles = 0;
-    plan->basis_doubles = (int64_t)plan->k_gram * nr::kWaveVec;
-    plan->stride = plan->basis_doubles + (plan->big ? 5 * (int64_t)k_max : 0);
-    plan->stride = (plan->stride + 31) / 32 * 32;
-    plan->g32_off = 0;
-    return NR_OK;
-  }
-  if (plan->k_gram <= nr::kSmallDim) {
-    // the small class (kernels.h): several small-workgroup items per CU;
-    // modules longer than its LDS vectors keep their per-node arrays in the
-    // slot's scratch
-    plan->variant = 5;
-    plan->m = nr::kSmallDim;
-    plan->kvec = nr::kSmallDim;
-    plan->big = k_max > nr::kSmallDim;
-    plan->per_cu = nr::profile_small_per_cu();
-    plan->slots = (int)std::max<int64_t>(1, std::min<int64_t>(n_items, (int64_t)dev_cu * plan->per_cu));
-    plan->gram_doubles = nr::packed_gram_doubles(plan->k_gram + 1);
-    plan->basis_doubles = (int64_t)plan->k_gram * nr::kSmallDim;
-    plan->stride = plan->gram_doubles + plan->basis_doubles + (plan->big ? 5 * (int64_t)k_max : 0);
-    plan->stride = (plan->stride + 31) / 32 * 32;
-    plan->g32_off = plan->stride;
-    plan->stride += (plan->gram_doubles / 2 + 31) / 32 * 32;
-    return NR_OK;
-  }
-  const int mg = profile_m_max(plan->k_gram);
-  plan->m = mg;
-  int kvec = k_max;
-  plan->big = false;
-  if (nr::profile_kernel_lds(kvec, mg, n_samples, 2) > 160 * 1024) {
-    // Large modules on the packed Gram too (half the Lanczos bytes of the
-    // full ld x ld Gram): LDS vectors as long as fit, and the per-node arrays
-    // of modules longer than them in the slot's scratch, as long as every
-    // Lanczos dimension min(k, S) fits the vectors.
-    int kp = (k_max + 15) / 16 * 16;
-    while (kp > 16 && nr::profile_kernel_lds(kp, mg, n_samples, 2) > 160 * 1024) kp -= 16;
-    if (plan->k_gram <= kp) {
-      kvec = kp;
-      plan->big = k_max > kp;
-    } else {
-      variant = 0;
-    }
-  }
-  // Large modules: the per-wave matvec partials (4 x k doubles) move from LDS
-  // to the slot's scratch, which leaves LDS for the six Lanczos vectors only.
-  if (variant == 0 && nr::profile_kernel_lds(kvec, mg, n_samples, 0) > 160 * 1024) variant = 4;
-  // Modules beyond even those vectors (any k up to N, as src/netStats.cpp:
-  // 217-280): Lanczos runs on the dual Gram (dimension S <= kvec) and their
-  // per-node arrays live in the slot's scratch; where the Lanczos dimension
-  // min(k, S) itself can exceed the LDS vectors (S > kvec), every vector and
-  // the index set move to the slot's scratch too (variant 6: no size limit
-  // but device memory).
-  if (variant == 4 && nr::profile_kernel_lds(kvec, mg, n_samples, 4) > 160 * 1024) {
-    kvec = nr::profile_kvec_max(mg);
-    if (n_samples > kvec) {
-      variant = 6;
-      kvec = k_max;
-    } else {
-      plan->big = true;
-    }
-  }
-  plan->kvec = kvec;
-  const size_t lds = nr::profile_kernel_lds(kvec, mg, n_samples, variant);
-  if (lds > 160 * 1024)
+  if (!nr::plan_profile(n_items, k_max, n_samples, data_doubles, dev_cu, plan))
     return fail(ctx, NR_ERR_UNSUPPORTED, "module too large for the summary-profile kernel's LDS budget");
-  const int want = variant == 4 || variant == 6 ? 1 : 3;
-  const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(want, (160 * 1024) / lds));
-  plan->variant = variant;
-  plan->per_cu = per_cu;
-  plan->slots = (int)std::max<int64_t>(1, std::min<int64_t>(n_items, (int64_t)dev_cu * per_cu));
-  if (variant == 2) {
-    const int64_t kc = plan->k_gram + 1;
-    plan->gram_doubles = nr::packed_gram_doubles((int)kc);  // packed triangle in chunked column groups
-  } else {
-    const int64_t ld = gram_ld(plan->k_gram);
-    plan->gram_doubles = ld * ld;
-  }
-  plan->basis_doubles = (int64_t)plan->k_gram * mg;
-  plan->stride = plan->gram_doubles + plan->basis_doubles +
-                 (variant == 4 || variant == 6 ? (int64_t)nr::kProfileWaves * kvec : 0) +
-                 (plan->big ? 5 * (int64_t)k_max : 0) +  // x.u, means, squares, contributions, index set
-                 (variant == 6 ? 6 * (int64_t)kvec + (kvec + 1) / 2 : 0);  // six vectors + index set
-  plan->g32_off = 0;
-  if (variant == 2) {  // fp32 copy of the packed Gram at the slot's end (relaxed Lanczos steps)
-    plan->stride = (plan->stride + 31) / 32 * 32;
-    plan->g32_off = plan->stride;
-    plan->stride += (plan->gram_doubles / 2 + 31) / 32 * 32;
-  }
   return NR_OK;
 }
 
@@ -278,58 +144,51 @@ int launch_profiles(nr_ctx* ctx, nr::ProfileParams pp, const int32_t* d_order,
   while (n_big < n_mod && k_sorted[n_big] > nr::kPackedLayoutK) ++n_big;
   struct Seg {
     int first, count;
-    ProfilePlan plan;
+    nr::ProfilePlan plan;
   } seg[2];
   int ns = 0;
   if (n_big > 0) seg[ns++] = {0, n_big, {}};
   if (n_big < n_mod) seg[ns++] = {n_big, n_mod - n_big, {}};
   // every segment's scratch (slots x stride) is one allocation, carved in turn
   int64_t total = 0;
-  bool fuse[2] = {false, false};
-  int fuse_kind[2] = {0, 0};  // ProfileParams::fused
   for (int i = 0; i < ns; ++i) {
-    const int rc = plan_profile(ctx, (int64_t)seg[i].count * n_perm, k_sorted[seg[i].first], (int)pp.n_samples,
-                                &seg[i].plan, pp.ones_off + 2 * pp.n_samples);
-    if (rc) return rc;
-    // Gram table: the packed class (compile-time layout, no dual items) takes
-    // its network statistics and Gram from the table's gathers, on the table
-    // kernel's own workgroup shape
     const int k_max = k_sorted[seg[i].first];
-    const bool fuse_table = table_np && table_np->es == 2 && seg[i].plan.variant == 2 &&
-                            k_max <= nr::kPackedLayoutK && k_max <= pp.n_samples &&
-                            nr::fused_net_fits(nr::kPackedLayoutK, std::min(nr::kPackedLayoutK, 160), nr::kTableWaves);
-    fuse_kind[i] = fuse_table ? 1 : 0;
-    fuse[i] = fuse_kind[i] != 0;
+    const int rc = plan_profile(ctx, (int64_t)seg[i].count * n_perm, k_max, (int)pp.n_samples, &seg[i].plan,
+                                pp.ones_off + 2 * pp.n_samples);
+    if (rc) return rc;
+    // Gram table: the segment that takes it has its network statistics and
+    // Gram from the table's gathers, on the table kernel's own workgroup shape
+    if (table_np && table_np->es == 2 && nr::profile_takes_table(seg[i].plan, k_max, pp.n_samples))
+      nr::profile_use_table(&seg[i].plan);
     total = std::max<int64_t>(total, seg[i].plan.stride * seg[i].plan.slots);
   }
   // segments run one after the other on one stream: they share the scratch
   if (int rc = ensure(ctx, *ln.scratch, *ln.scratch_cap, (size_t)total)) return rc;
   for (int i = 0; i < ns; ++i) {
-    const ProfilePlan& plan = seg[i].plan;
-    const int k_max = k_sorted[seg[i].first];
+    const nr::ProfilePlan& plan = seg[i].plan;
     pp.mod_order = d_order + seg[i].first;
     pp.n_items = (int32_t)((int64_t)seg[i].count * n_perm);
-    pp.k_max = k_max;
-    pp.ld = gram_ld(plan.k_gram);
+    pp.k_max = k_sorted[seg[i].first];
+    pp.ld = plan.ld;
     pp.m_max = plan.m;
     pp.kvec = plan.kvec;
     pp.basis_doubles = plan.basis_doubles;
     pp.gram_doubles = plan.gram_doubles;
     pp.scratch = *ln.scratch;
     pp.scratch_stride = plan.stride;
-    pp.part_global = plan.variant == 4 || plan.variant == 6 ? 1 : 0;
-    pp.vec_global = plan.variant == 6 ? 1 : 0;
+    pp.part_global = plan.part_global;
+    pp.vec_global = plan.vec_global;
     pp.order_tail =
         profile_order_tail(plan.slots, k_sorted, seg[i].first, seg[i].count, n_perm, (int)pp.n_samples);
     pp.g32_off = plan.g32_off;
-    pp.fused = fuse_kind[i];
+    pp.fused = plan.kernel == nr::ProfileKernel::Table;
     if (pp.fused) {
       pp.net = *table_np;
       pp.net.mod_order = pp.mod_order;
       if (fused_from) *fused_from = seg[i].first;
     }
     NR_HIP(ctx, hipMemsetAsync(pp.queue, 0, sizeof(int), st));
-    NR_HIP(ctx, nr::launch_profile(pp, plan.slots, plan.variant, plan.per_cu, st));
+    NR_HIP(ctx, nr::launch_profile(pp, plan, st));
   }
   return NR_OK;
 }
@@ -635,9 +494,9 @@ int launch_batch(nr_ctx* ctx, const nr::IndexSource& src, int64_t n_perm, double
 // the numerical path of a dataset/module set is fixed (the table path and the
 // per-item matrix-core Gram differ at the 1e-12 level): the table is built
 // when (1) the packed-class segment (modules of <= 320 nodes) would be ONE
-// fused launch of the packed kernel, i.e. launch_profiles' own rule: its
-// plan is variant 2 (not the small class, min(k, S) > 112) and none of its
-// modules has more nodes than samples; (2) that segment carries at least
+// fused launch of the table kernel, by the rule launch_profiles applies
+// (nr::profile_takes_table: the packed class, so min(k, S) > 112, and none of
+// its modules with more nodes than samples); (2) that segment carries at least
 // half of the present modules' Gram work; (3) n^2 fits kTableMaxElems (the
 // build holds 56 bytes per matrix element: pairs, X^T X and the table). A
 // failed allocation is NR_ERR_OOM, not a silent switch to the other path.
@@ -668,10 +527,9 @@ bool table_wanted(nr_ctx* ctx) {
     if (hipDeviceTotalMem(&total, ctx->device) != hipSuccess) return false;
     if ((double)n * (double)n * 56.0 > 0.6 * (double)total) return false;
   }
-  ProfilePlan plan;
+  nr::ProfilePlan plan;
   if (plan_profile(ctx, 1, packed_max, (int)S, &plan, (int64_t)n * S + 2 * (int64_t)S) != NR_OK) return false;
-  return plan.variant == 2 &&
-         nr::fused_net_fits(nr::kPackedLayoutK, std::min(nr::kPackedLayoutK, 160), nr::kTableWaves);
+  return nr::profile_takes_table(plan, packed_max, S);
 }
 
 int maybe_build_table(nr_ctx* ctx) {

@@ -3,11 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "profile_plan.h"
+
 namespace nr {
 
 enum { NR_IDX_PRP = 0, NR_IDX_TABLE = 1, NR_IDX_DIRECT = 2 };
 
-constexpr int kProfileWaves = 4;  // waves of the 256-thread profile workgroup (NR_WAVES)
 constexpr int kPackedLayoutK = 320;  // modules of the packed kernel's compile-time LDS layout
 
 // phase-stamp slots of the summary-profile kernel (nr_set_stamps)
@@ -19,7 +20,8 @@ constexpr int NR_N_STAMPS = 16;
 // longer than kSmallDim in the slot's scratch.
 constexpr int kSmallDim = 112;
 constexpr int kSmallWaves = 2;  // (one wave per item measured slower: profiles/r03/small_class/)
-// The wave class (round 5, variant 7): Lanczos dimension at most kWaveDim, one
+constexpr int kSmallOcc = 3;    // its waves per SIMD (launch bound): 12 waves per CU
+// The wave class (round 5, ProfileClass::Wave): Lanczos dimension at most kWaveDim, one
 // wave per item with the item's whole Gram in its registers (kernels.hip).
 constexpr int kWaveBlocks = 7;                // 16-row blocks of the Gram's side (<= 112)
 constexpr int kWaveVec = 16 * kWaveBlocks;     // LDS vector length and Lanczos basis columns
@@ -101,7 +103,7 @@ struct ProfileParams {
   int64_t g32_off;             // doubles from the slot start to the fp32 copy of the packed Gram
                                // (relaxed Lanczos steps; 0: no copy, fp64 matvecs throughout)
   int32_t vec_global;          // 1: the Lanczos vectors, per-node arrays and index set in the slot's
-                               // scratch too (Lanczos dimensions beyond the LDS vectors: variant 6)
+                               // scratch too (ProfileClass::FullVectorsInScratch)
   int32_t order_tail;          // queue order: 0 = module-major (large modules first); T > 0 =
                                // permutation-major over all modules (a size mix in flight) for the
                                // first n_perm - T permutations, the last T module-major
@@ -174,19 +176,10 @@ hipError_t launch_sweep(const SweepParams& P, hipStream_t st);
 size_t net_kernel_lds(int k_max);
 bool net_kernel_big(int k_max);        // per-node arrays in global scratch
 size_t net_big_slot_bytes(int k_max);  // global scratch per workgroup in that mode
-size_t profile_kernel_lds(int k_max, int m_max, int n_samples, int variant);
-// Doubles of the packed (chunked column-group) Gram of side kc, rounded to 32.
-int64_t packed_gram_doubles(int kc);
-int profile_kvec_max(int m_max);  // longest LDS vectors of the large-module layout (variant 4)
 hipError_t launch_net(const NetParams& P, int64_t n_items, hipStream_t st);
-// Whether the packed kernel's LDS (vectors of kvec, basis mmax) holds the
-// network item's per-node arrays (the fused Gram-table path).
-bool fused_net_fits(int kvec, int mmax, int nw);
 // waves per workgroup of the Gram-table kernel (2 waves x 5 per CU measured
-// 13% slower, profiles/r03/table_waves/), its LDS bytes and workgroups per CU
+// 13% slower, profiles/r03/table_waves/)
 constexpr int kTableWaves = 4;
-size_t profile_table_lds();
-int profile_table_per_cu();
 // The Gram table of a dataset with data: gram[i + j n] = x_i . x_j over the
 // n_samples rows of X (n_samples x (n + 2), the virtual columns behind), and
 // colsum[j] = sum of column j.
@@ -195,17 +188,9 @@ hipError_t launch_gram_full(const double* X, int64_t S, int64_t n, double* gram,
 // out[2e] = in[e], out[2e + 1] = {gram[e], net(j, i)} for e = i + j n.
 hipError_t launch_widen_pairs(const double2* in, const double* gram, double2* out, int64_t n, int symmetric,
                               hipStream_t st);
-// the small class (variant 5): its LDS bytes per workgroup and workgroups per CU
-size_t profile_small_lds();
-int profile_small_per_cu();
-// the wave class (variant 7): its LDS bytes per workgroup and workgroups per CU
-size_t profile_wave_lds();
-int profile_wave_per_cu();
-// variant 0 full Gram, 2 packed Gram, 4 full Gram with the partials in scratch,
-// 5 the small class, 6 full Gram with the partials and every vector in scratch,
-// 7 the wave class (register-resident Gram)
-hipError_t launch_profile(const ProfileParams& P, int n_slots, int variant, int wg_per_cu,
-                          hipStream_t st);
+// One summary-profile launch as planned (profile_plan.h): plan.kernel on
+// plan.slots workgroups of plan.block threads and plan.lds bytes of LDS.
+hipError_t launch_profile(const ProfileParams& P, const ProfilePlan& plan, hipStream_t st);
 hipError_t launch_interleave(const double* corr, const double* net, double2* out, int64_t n_elem,
                              hipStream_t st);
 hipError_t launch_symmetry(const double2* a, int64_t n, int* asym, hipStream_t st);

@@ -83,9 +83,8 @@ struct NetLds {
   __device__ __forceinline__ static int at(int i) { return i + (i >> 5); }
 };
 
-// Slots per per-node array (NetLds::at).
-__host__ __device__ __forceinline__ int net_kpad(int kmax) { return kmax + (kmax >> 5) + 1; }
-
+// net_kpad(kmax) slots per per-node array (NetLds::at), net_lds_bytes in all:
+// device_common.h.
 template <int NW>
 __device__ __forceinline__ NetLds carve_net_lds(unsigned char* smem, int kmax) {
   NetLds L;
@@ -121,12 +120,6 @@ __device__ __forceinline__ NetLds carve_net_over(double* region, double* red, ui
   L.red = red;
   L.idx = idx;
   return L;
-}
-
-size_t net_lds_bytes(int nw, int kmax) {
-  const size_t kp = (size_t)net_kpad(kmax);
-  return sizeof(double) * (8 * (size_t)nw + (size_t)(nw + 2) * kp) + sizeof(unsigned long long) * 3 * kp +
-         sizeof(int) * ((size_t)kmax + 2 * kp);
 }
 
 // One weighted-degree contribution a = |net(source, target)| (a >= 0).
@@ -268,12 +261,8 @@ __device__ __forceinline__ int64_t pair_at(int64_t r, int64_t c, int64_t n, int6
 // a global (not constant) cell, so the discovery-load pointer stays a global pointer
 __device__ double kNetNanCell = __builtin_nan("");
 
-// The packed symmetric Gram's addressing (layout described at
-// packed_gram_doubles below).
-__host__ __device__ __forceinline__ int pk_groups(int kc) { return (kc + 15) >> 4; }
-__host__ __device__ __forceinline__ int64_t pk_base(int g, int P) {
-  return 16 * (int64_t)g * P - 128 * (int64_t)g * (g - 1);
-}
+// The packed symmetric Gram's addressing (layout described at pk_store_tile
+// below; pk_groups, pk_base: device_common.h).
 __device__ __forceinline__ int64_t pk_at(int r, int c, int kc) {  // r >= 16 (c / 16)
   const int g = c >> 4;
   const int rr = r - 16 * g;
@@ -793,10 +782,6 @@ __device__ __forceinline__ void pk_store_tile(double* G, float* G32, int kc, int
       if (G32) G32[base + t * h] = (float)x;  // the relaxed-phase copy (packed_matvec<NW, true>)
     }
   }
-}
-
-int64_t packed_gram_doubles(int kc) {
-  return (pk_base(pk_groups(kc), kc) + 31) / 32 * 32;
 }
 
 // G = [X 1]^T [X 1] over the k module columns of X (S x N, column-major) plus a
@@ -2082,7 +2067,7 @@ __device__ __forceinline__ void profile_body(const ProfileParams& P) {
   const int mmax = KB > 0 ? (MB > 0 ? MB : (KB < 160 ? KB : 160)) : P.m_max;
   const int S = (int)P.n_samples;
   double* part;
-  // Large modules (variant 4, !PACKED only): the per-wave matvec partials live
+  // Large modules (the full-Gram classes, !PACKED only): the per-wave matvec partials live
   // in the slot's scratch behind the basis; the workgroup's barriers order
   // them (one CU, one vector L1).
   const bool pglob = !PACKED && P.part_global;
@@ -2092,7 +2077,7 @@ __device__ __forceinline__ void profile_body(const ProfileParams& P) {
   double* G = P.scratch + (int64_t)blockIdx.x * P.scratch_stride;  // Gram
   const int ld = P.ld;
   double* Q = G + P.gram_doubles;                                  // Lanczos basis
-  // variant 6: every vector in the slot's scratch behind the partials
+  // FullVectorsInScratch: every vector in the slot's scratch behind the partials
   const bool vglob = !PACKED && P.vec_global;
   part = nullptr;
   const LzLds L = vglob ? carve_split<NW>(smem, Q + P.basis_doubles + (int64_t)NW * kmax, kmax, mmax)
@@ -2252,7 +2237,6 @@ module_profile_table_kernel(ProfileParams P) {
 // execution unit: the 168-VGPR budget of the packed kernel), as many items
 // per CU as the LDS holds. (Computing the items' network statistics in the
 // same workgroups measured 1.6x slower on C2, profiles/r04/ab2/.)
-constexpr int kSmallOcc = 3;
 template <int NW>
 __global__ void __launch_bounds__(NW * 64, kSmallOcc)
 module_profile_small_kernel(ProfileParams P) {
@@ -2522,18 +2506,6 @@ __device__ __forceinline__ bool wave_start_column(const nr_f64x4 (&T)[kWaveTiles
   }
   nr_sync<1>();
   return ok;
-}
-
-// LDS of the wave kernel: carve_lds<1> with vectors of kWaveVec, a basis of
-// kWaveVec columns, and three extra vectors (ylo, yup, the Gram diagonal).
-size_t profile_wave_lds() {
-  constexpr size_t kv = kWaveVec, mb = kWaveVec;
-  return sizeof(double) * (8 + 6 * kv + 3 * kv + 4 * mb + 5 * mb + 3 * (mb + 1)) + sizeof(uint32_t) * kv;
-}
-
-int profile_wave_per_cu() {
-  const int by_lds = (int)((160 * 1024) / profile_wave_lds());
-  return by_lds < 4 ? by_lds : 4;  // one wave per SIMD (the Gram's registers)
 }
 
 __global__ void __launch_bounds__(64, 1)
@@ -2825,70 +2797,15 @@ __global__ void export_indices_kernel(IndexSource src, int64_t n_nodes_total, in
 // ---------------------------------------------------------------------------
 // Four waves per item unless their per-wave weighted-degree copies would not
 // fit the LDS (modules of more than ~1,900 nodes): then two.
-int net_kernel_waves(int k_max) { return net_lds_bytes(4, k_max) <= 160 * 1024 ? 4 : 2; }
+int net_kernel_waves(int k_max) { return net_lds_bytes(4, k_max) <= kLdsBudget ? 4 : 2; }
 
-bool net_kernel_big(int k_max) { return net_lds_bytes(2, k_max) > 160 * 1024; }
+bool net_kernel_big(int k_max) { return net_lds_bytes(2, k_max) > kLdsBudget; }
 
 size_t net_kernel_lds(int k_max) {
   return net_kernel_big(k_max) ? sizeof(double) * 8 * 4 : net_lds_bytes(net_kernel_waves(k_max), k_max);
 }
 
 size_t net_big_slot_bytes(int k_max) { return (net_lds_bytes(4, k_max) + 255) / 256 * 256; }
-
-// Compile-time module-size bucket of the packed kernel (0 = runtime layout).
-int packed_bucket(int k_max) { return k_max <= kPackedLayoutK ? kPackedLayoutK : 0; }
-
-// variant: 0 full Gram, 2 packed Gram, 4 full Gram with the matvec partials
-// in global scratch (all 4-wave workgroups)
-int profile_kvec_max(int m_max) {
-  const size_t fixed = sizeof(double) * (8 * NR_WAVES + 12 * (size_t)m_max + 3);
-  const size_t per = 6 * sizeof(double) + sizeof(uint32_t);
-  return (int)((160 * 1024 - fixed) / per) / 16 * 16;
-}
-
-size_t profile_kernel_lds(int k_max, int m_max, int n_samples, int variant) {
-  (void)n_samples;
-  if (variant == 6)  // reduction scratch + tridiagonal arrays only (carve_split)
-    return sizeof(double) * (8 * NR_WAVES + 12 * (size_t)m_max + 3);
-  if (variant == 4)  // full Gram, matvec partials in global scratch
-    return sizeof(double) * (8 * NR_WAVES + 6 * (size_t)k_max + 12 * (size_t)m_max + 3) + sizeof(uint32_t) * k_max;
-  const bool packed = variant != 0;
-  const int nw = NR_WAVES;
-  if (packed && packed_bucket(k_max) > 0) {
-    k_max = packed_bucket(k_max);
-    m_max = k_max < 160 ? k_max : 160;
-  }
-  if (packed)  // the partials double as twork (packed_part_doubles)
-    return sizeof(double) * (8 * nw + 6 * (size_t)k_max + packed_part_doubles(nw, k_max, m_max) + 7 * (size_t)m_max + 3) +
-           sizeof(uint32_t) * k_max;
-  return sizeof(double) * (8 * nw + (6 + (size_t)nw) * (size_t)k_max + 12 * (size_t)m_max + 3) +
-         sizeof(uint32_t) * k_max;
-}
-
-size_t profile_table_lds() {
-  constexpr int nw = kTableWaves, kb = kPackedLayoutK, mb = kPackedLayoutK < 160 ? kPackedLayoutK : 160;
-  return sizeof(double) * (8 * nw + 6 * (size_t)kb + packed_part_doubles(nw, kb, mb) + 7 * (size_t)mb + 3) +
-         sizeof(uint32_t) * kb;
-}
-
-int profile_table_per_cu() {
-  const int by_lds = (int)((160 * 1024) / profile_table_lds());
-  const int by_waves = 12 / kTableWaves;
-  return by_lds < by_waves ? by_lds : by_waves;
-}
-
-size_t profile_small_lds() {
-  constexpr int nw = kSmallWaves, kb = kSmallDim, mb = kSmallDim;
-  return sizeof(double) * (8 * nw + 6 * (size_t)kb + packed_part_doubles(nw, kb, mb) + 7 * (size_t)mb + 3) +
-         sizeof(uint32_t) * kb;
-}
-
-// items per CU: the LDS bound, at most 12 waves (the kernel's 168-VGPR budget)
-int profile_small_per_cu() {
-  const int by_lds = (int)((160 * 1024) / profile_small_lds());
-  const int by_waves = 4 * kSmallOcc / kSmallWaves;
-  return by_lds < by_waves ? by_lds : by_waves;
-}
 
 hipError_t launch_net(const NetParams& P0, int64_t n_items, hipStream_t st) {
   NetParams P = P0;
@@ -2921,34 +2838,31 @@ hipError_t launch_net(const NetParams& P0, int64_t n_items, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_profile(const ProfileParams& P, int n_slots, int variant, int wg_per_cu,
-                          hipStream_t st) {
-  const size_t lds = profile_kernel_lds(P.kvec > 0 ? P.kvec : P.k_max, P.m_max, (int)P.n_samples, variant);
-  const dim3 g((unsigned)n_slots), b4(NR_BS);
-  if (variant == 2) {
-    // the compile-time layout of modules of <= 320 nodes at three workgroups
-    // per CU (measured fastest: profiles/r02/profile_variants.txt), else the
-    // runtime layout
-    if (P.fused == 1 && packed_bucket(P.k_max) == kPackedLayoutK && wg_per_cu >= 3)
-      hipLaunchKernelGGL(module_profile_table_kernel, g, dim3(64 * kTableWaves), profile_table_lds(), st, P);
-    else if (packed_bucket(P.k_max) == kPackedLayoutK && wg_per_cu >= 3)
-      hipLaunchKernelGGL((module_profile_packed4_kernel<kPackedLayoutK, 3>), g, b4, lds, st, P);
-    else if (wg_per_cu == 1 && !P.fused)
-      hipLaunchKernelGGL(module_profile_big_kernel, g, b4, lds, st, P);
-    else
-      hipLaunchKernelGGL((module_profile_packed4_kernel<0, 2>), g, b4, lds, st, P);
-    return hipGetLastError();
+hipError_t launch_profile(const ProfileParams& P, const ProfilePlan& plan, hipStream_t st) {
+  const dim3 g((unsigned)plan.slots), b((unsigned)plan.block);
+  switch (plan.kernel) {
+    case ProfileKernel::FullGram:
+      hipLaunchKernelGGL(module_profile_kernel, g, b, plan.lds, st, P);
+      break;
+    case ProfileKernel::PackedFixed:
+      hipLaunchKernelGGL((module_profile_packed4_kernel<kPackedLayoutK, 3>), g, b, plan.lds, st, P);
+      break;
+    case ProfileKernel::PackedRuntime:
+      hipLaunchKernelGGL((module_profile_packed4_kernel<0, 2>), g, b, plan.lds, st, P);
+      break;
+    case ProfileKernel::PackedBig:
+      hipLaunchKernelGGL(module_profile_big_kernel, g, b, plan.lds, st, P);
+      break;
+    case ProfileKernel::Table:
+      hipLaunchKernelGGL(module_profile_table_kernel, g, b, plan.lds, st, P);
+      break;
+    case ProfileKernel::Small:
+      hipLaunchKernelGGL((module_profile_small_kernel<kSmallWaves>), g, b, plan.lds, st, P);
+      break;
+    case ProfileKernel::Wave:
+      hipLaunchKernelGGL(module_profile_wave_kernel, g, b, plan.lds, st, P);
+      break;
   }
-  if (variant == 7) {
-    hipLaunchKernelGGL(module_profile_wave_kernel, g, dim3(64), profile_wave_lds(), st, P);
-    return hipGetLastError();
-  }
-  if (variant == 5) {
-    hipLaunchKernelGGL((module_profile_small_kernel<kSmallWaves>), g, dim3(64 * kSmallWaves), profile_small_lds(),
-                       st, P);
-    return hipGetLastError();
-  }
-  hipLaunchKernelGGL(module_profile_kernel, g, b4, lds, st, P);
   return hipGetLastError();
 }
 
@@ -2974,15 +2888,6 @@ hipError_t launch_widen_pairs(const double2* in, const double* gram, double2* ou
   const unsigned nb = (unsigned)((n + 31) / 32);
   hipLaunchKernelGGL(widen_pairs_kernel, dim3(nb, nb), dim3(256), 0, st, in, gram, out, n, symmetric);
   return hipGetLastError();
-}
-
-bool fused_net_fits(int kvec, int mmax, int nw) {
-  // NetLds (carve_net_over, from L.q; its reduction scratch is L.red) against
-  // the LzLds span from q up to idx (carve_lds, twork in the partials)
-  const size_t need = net_lds_bytes(nw, kvec) - sizeof(double) * 8 * nw;
-  const size_t have = sizeof(double) * (6 * (size_t)kvec + (size_t)packed_part_doubles(nw, kvec, mmax) +
-                                        4 * (size_t)mmax + 3 * ((size_t)mmax + 1));
-  return need <= have;
 }
 
 hipError_t launch_symmetry(const double2* a, int64_t n, int* asym, hipStream_t st) {

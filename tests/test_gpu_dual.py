@@ -4,7 +4,10 @@ Lanczos on H = [X' 1]'[X' 1] gives the summary profile u directly
 from one pass over the data. Checked against the C++ LAPACK restatement
 (dgesvd of the S x k block) on identical shuffles, in vector mode (NetProps'
 summary profiles), through the non-finite (svd failure) path, and on the
-full-Gram layouts of modules beyond the packed kernel's 320-node layout."""
+classes of modules beyond the packed kernel's 320-node layout: the packed
+kernel's runtime layout, the full Gram with its matvec partials in scratch,
+and the same with every Lanczos vector in scratch (the planner's classes:
+netrep_amd/csrc/profile_plan.h)."""
 import numpy as np
 import pytest
 
@@ -53,9 +56,10 @@ def test_dual_gram_vs_cpp_oracle():
 
 def test_size_classes_vs_cpp_oracle():
     """Modules beyond the packed kernel's 320-node layout run in their own
-    launch on the full-Gram layout (S = 400 > k: primal, full Gram; k > S:
-    dual), the rest on the packed kernel -- one cube, every statistic at the
-    parity bar."""
+    launch: k = 520 at S = 400 plans as the packed Gram on the runtime LDS
+    layout at two workgroups per CU (the 520-node module dual, the 350- and
+    330-node ones primal), the rest on the packed kernel's compile-time
+    layout -- one cube, every statistic at the parity bar."""
     lay, mi, disc, txs, tc, tn = _case([520, 350, 330, 300, 120, 45], 400, 21)
     eng = _engine_from(mi, disc, txs, tc, tn)
     nulls = eng.run(3, 11, 7)
@@ -145,6 +149,25 @@ def test_lanczos_dimension_beyond_lds_vectors(sizes, n_samples, seed, n_nodes):
     exp, obs = _cpp(mi, disc, txs, tc, tn, pis)
     assert_stats_close(eng.observed(), obs, what=f"observed (k {sizes[0]}, S {n_samples})")
     assert_stats_close(nulls, exp, what=f"nulls (k {sizes[0]}, S {n_samples})")
+
+
+@pytest.mark.parametrize("sizes", [[1744, 40], [2560, 40]])
+def test_full_gram_partials_in_scratch_vs_cpp_oracle(sizes):
+    """The class between the packed Gram and variant 6: a Lanczos dimension
+    min(k, S) beyond the packed layout's 1,728-long LDS vectors that still
+    fits the full-Gram layout's (<= 2,544) once the matvec partials sit in the
+    slot's scratch. 1,744 nodes at S = 1,744: primal, LDS vectors of k. 2,560
+    nodes at S = 1,744: dual, LDS vectors of 2,544, the module's per-node
+    arrays in scratch too. The smallest shapes that reach the class; one
+    permutation. Against the C++ LAPACK restatement on the identical shuffle."""
+    lay, mi, disc, txs, tc, tn = _case(sizes, 1744, 41, n_nodes=3000)
+    eng = _engine_from(mi, disc, txs, tc, tn)
+    nulls = eng.run(0, 1, 31)
+    pis = N.prp_table(31, 0, 1, mi.null_idx.size)
+    exp, obs = _cpp(mi, disc, txs, tc, tn, pis)
+    e_obs = assert_stats_close(eng.observed(), obs, what=f"observed (k {sizes[0]}, S 1744)")
+    e_null = assert_stats_close(nulls, exp, what=f"nulls (k {sizes[0]}, S 1744)")
+    print(f"k {sizes[0]}, S 1744: max scaled error observed {e_obs:.3e}, nulls {e_null:.3e}")
 
 
 def test_lanczos_beyond_lds_mixed_sizes_multi_slot():

@@ -345,9 +345,10 @@ def test_large_modules_vs_cpp_oracle(seed):
 
 def test_c5_sized_modules_vs_cpp_oracle():
     """C5-shaped modules (BASELINE configs[4]: up to 2,000 nodes at S = 1,000,
-    so k > S): the large-module layout (full Gram, matvec partials in global
-    scratch, 320-vector Lanczos basis, network statistics as their own
-    kernel) against the C++ restatement (LAPACK dgesvd) on identical shuffles,
+    so k > S): k = 2,000 at S = 1,000 plans as the packed Gram at one
+    workgroup per CU with 1,728-long LDS vectors, the longer modules' per-node
+    arrays in the slot's scratch (320-vector Lanczos basis, network statistics
+    as their own kernel) against the C++ restatement (LAPACK dgesvd) on identical shuffles,
     observed values through IntermediateProperties-shaped discovery vectors."""
     from netrep_amd import synthetic as S
     from oracle import ref_cpp
