@@ -176,13 +176,11 @@ int launch_profiles(nr_ctx* ctx, nr::ProfileParams pp, const int32_t* d_order,
     pp.gram_doubles = plan.gram_doubles;
     pp.scratch = *ln.scratch;
     pp.scratch_stride = plan.stride;
-    pp.part_global = plan.part_global;
     pp.vec_global = plan.vec_global;
     pp.order_tail =
         profile_order_tail(plan.slots, k_sorted, seg[i].first, seg[i].count, n_perm, (int)pp.n_samples);
     pp.g32_off = plan.g32_off;
-    pp.fused = plan.kernel == nr::ProfileKernel::Table;
-    if (pp.fused) {
+    if (plan.kernel == nr::ProfileKernel::Table) {
       pp.net = *table_np;
       pp.net.mod_order = pp.mod_order;
       if (fused_from) *fused_from = seg[i].first;

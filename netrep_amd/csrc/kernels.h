@@ -9,23 +9,8 @@ namespace nr {
 
 enum { NR_IDX_PRP = 0, NR_IDX_TABLE = 1, NR_IDX_DIRECT = 2 };
 
-constexpr int kPackedLayoutK = 320;  // modules of the packed kernel's compile-time LDS layout
-
 // phase-stamp slots of the summary-profile kernel (nr_set_stamps)
 constexpr int NR_N_STAMPS = 16;
-
-// The small class of summary-profile items: Lanczos dimension min(k, S) at
-// most kSmallDim, solved by workgroups of kSmallWaves waves (several items per
-// CU in flight instead of three 4-wave items); per-node arrays of modules
-// longer than kSmallDim in the slot's scratch.
-constexpr int kSmallDim = 112;
-constexpr int kSmallWaves = 2;  // (one wave per item measured slower: profiles/r03/small_class/)
-constexpr int kSmallOcc = 3;    // its waves per SIMD (launch bound): 12 waves per CU
-// The wave class (round 5, ProfileClass::Wave): Lanczos dimension at most kWaveDim, one
-// wave per item with the item's whole Gram in its registers (kernels.hip).
-constexpr int kWaveBlocks = 7;                // 16-row blocks of the Gram's side (<= 112)
-constexpr int kWaveVec = 16 * kWaveBlocks;     // LDS vector length and Lanczos basis columns
-constexpr int kWaveDim = kWaveVec - 1;         // the side is the dimension plus the ones column
 
 // Where the test column of module node c comes from.
 struct IndexSource {
@@ -96,7 +81,6 @@ struct ProfileParams {
   int* queue;                  // work-queue head, zeroed before launch
   int* diag;                   // [0] Lanczos step-cap hits, [1] items, [2] Lanczos steps, [3] reorthogonalisations
   unsigned long long* stamps;  // [8] per-phase shader cycles (diagnostics; NULL = off)
-  int part_global;             // 1: matvec partials (4 x k_max) at the end of the slot's scratch
   int32_t kvec;                // LDS vector length (0: k_max); larger (dual) modules keep their
                                // per-node arrays in the slot's scratch
   int64_t basis_doubles;       // Lanczos basis doubles per slot (behind the Gram)
@@ -107,10 +91,8 @@ struct ProfileParams {
   int32_t order_tail;          // queue order: 0 = module-major (large modules first); T > 0 =
                                // permutation-major over all modules (a size mix in flight) for the
                                // first n_perm - T permutations, the last T module-major
-  // Gram table (packed kernel only): the network statistics of each item are
-  // computed in the profile workgroup from one gather per pair of the table,
-  // which also fills the item's packed Gram (no matrix-core Gram for k <= S)
-  int32_t fused;                // 1: Gram-table items (network statistics + Gram from the table)
+  // The Gram-table kernel only: each item's network statistics, from the one
+  // gather per pair of the table that also fills the item's packed Gram
   NetParams net;
 };
 
@@ -177,9 +159,6 @@ size_t net_kernel_lds(int k_max);
 bool net_kernel_big(int k_max);        // per-node arrays in global scratch
 size_t net_big_slot_bytes(int k_max);  // global scratch per workgroup in that mode
 hipError_t launch_net(const NetParams& P, int64_t n_items, hipStream_t st);
-// waves per workgroup of the Gram-table kernel (2 waves x 5 per CU measured
-// 13% slower, profiles/r03/table_waves/)
-constexpr int kTableWaves = 4;
 // The Gram table of a dataset with data: gram[i + j n] = x_i . x_j over the
 // n_samples rows of X (n_samples x (n + 2), the virtual columns behind), and
 // colsum[j] = sum of column j.

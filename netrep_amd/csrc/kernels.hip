@@ -431,11 +431,11 @@ __device__ __forceinline__ void net_process(const NetParams& P, const NetLds& L,
   }
 }
 
-// GRAM (the Gram-table items of the packed profile kernel): the item's packed
-// Gram is filled from the same gathers -- G_ij for every pair, the diagonal and
-// the ones column here -- into a region the caller zeroed; g1 / bad return
-// this thread's part of 1'G1 over the data block and a non-finite-diagonal flag.
-template <int NW, bool PIPE, bool SYM, bool GRAM = false, int U = 7, int ESC = -1, bool HD = false>
+// GRAM (the Gram-table kernel's items): the item's packed Gram is filled from
+// the same gathers -- G_ij for every pair, the diagonal and the ones column
+// here -- into a region the caller zeroed; g1 / bad return this thread's part
+// of 1'G1 over the data block and a non-finite-diagonal flag.
+template <int NW, bool PIPE, bool SYM, bool GRAM = false, int U = 7, int ESC = -1>
 __device__ __forceinline__ void net_item(const NetParams& P, int m, int64_t p_local, int64_t off, int64_t k,
                                          const NetLds& L, const GramOut& go = GramOut{}, double* g1_out = nullptr,
                                          int* bad_out = nullptr) {
@@ -461,7 +461,7 @@ __device__ __forceinline__ void net_item(const NetParams& P, int m, int64_t p_lo
       const double gcc = pairs[ad + 1].x;
       const double cs = P.colsum[ic];
       const int64_t a1 = pk_at((int)c, (int)c, go.kc), a2 = pk_at((int)k, (int)c, go.kc);
-      go.put(a1, HD ? 0.5 * gcc : gcc);  // HD: the packed diagonal is stored halved (packed_gram_doubles)
+      go.put(a1, 0.5 * gcc);  // GRAM implies the halved packed diagonal (HD, packed_gram_doubles)
       go.put(a2, cs);
       g1 += gcc;
       bad |= (int)!isfinite(gcc);
@@ -751,14 +751,15 @@ __device__ __forceinline__ double reorthogonalise_cgs(const double* __restrict__
 // fill halves at its store of the diagonal (net_item); whoever reads G_cc
 // itself doubles what is stored (start_column, profile_body's contributions).
 // The ones row (k, c) and the corner (k, k) are stored as they are.
-// Which of the two forms a packed Gram has depends on the kernel, not on who
-// filled it: HD is a compile-time flag of the kernel (profile_body: HD =
-// TABLE) that its fill, its matvec and its readers of G_cc all take. Every
-// other packed kernel keeps the plain diagonal and the matvec's test for it,
-// whether its Gram comes from the matrix cores (pk_store_tile,
-// pk_store_tile16) or, in a fused launch of the packed 4-wave kernel
-// (P.fused == 1), from the same table fill with HD = false. A packed Gram
-// never leaves the kernel that filled it.
+// HD is a compile-time flag of the kernel (profile_body: the Gram source is
+// the table) that its fill, its matvec and its readers of G_cc all take. Every
+// other packed kernel fills its Gram on the matrix cores (pk_store_tile,
+// pk_store_tile16) and keeps the plain diagonal, the matvec's test for it and
+// with them its outputs bit for bit: one null of
+// tests/test_gpu_small.py::test_small_class_primal_only_vs_cpp_oracle (a
+// near-degenerate top eigenpair) sits at 9.8e-11 of the oracle against the
+// 1e-10 bar, and the halved diagonal's rounding moved it to 1.1e-10.
+// A packed Gram never leaves the kernel that filled it.
 
 // Stores one 16 x 16 MFMA accumulator tile of the Gram's super-tile (I2, J2)
 // into the packed layout: lane (i16, kk) holds rows gj = 32 J2 + 16 b + i16 of
@@ -2032,64 +2033,52 @@ __device__ __forceinline__ void lanczos_ritz(const ProfileParams& P, int k, cons
   NR_STAMP(10);  // Ritz vector
 }
 
-
-
-
-
 // ---------------------------------------------------------------------------
 // Scheme 1 (global scratch): G in the workgroup's scratch slot, full (both
 // triangles) or packed symmetric; the Lanczos matvecs stream it from L2 /
 // Infinity Cache. Any module size that fits the LDS vectors.
-// KB > 0 fixes the LDS layout at compile time for modules of at most KB nodes
-// (every carve-out an immediate offset; frees the SGPRs runtime offsets cost).
+// The kernel's shape is profile_traits(K) (profile_plan.h), which the planner
+// sizes the launch from. kb > 0 fixes the LDS layout at compile time for
+// modules of at most kb nodes (every carve-out an immediate offset; frees the
+// SGPRs runtime offsets cost). Only the Gram source it names is compiled in:
+// no matrix-core or dual Gram in the table kernel, no table fill in the
+// others, which keeps the register demand down (spills at the 168-VGPR budget).
 // ---------------------------------------------------------------------------
-// TABLE: a launch whose items all take the Gram-table path (P.fused, no dual
-// items): the matrix-core and dual Gram code is not compiled in, which lowers
-// the register demand of the kernel (its spills at the 168-VGPR budget).
-// G64: the large modules' 64 x 64 per-wave super-tile Gram (one workgroup per
-// CU); a kernel holds one Gram variant, else the compiler merges the
-// variants' MFMA blocks and spills around them.
-template <int NW, bool PACKED, int KB, int MB = 0, bool TABLE = false, bool G64 = false>
+template <ProfileKernel K>
 __device__ __forceinline__ void profile_body(const ProfileParams& P) {
-  constexpr int BS = NW * 64;
-  // The packed Gram's diagonal stored halved (packed_gram_doubles): the
-  // Gram-table kernel. The matrix-core kernels keep the plain diagonal, and
-  // with it their outputs bit for bit: one null of
-  // tests/test_gpu_small.py::test_small_class_primal_only_vs_cpp_oracle (a
-  // near-degenerate top eigenpair) sits at 9.8e-11 of the oracle against the
-  // 1e-10 bar, and the halved diagonal's rounding moved it to 1.1e-10.
-  constexpr bool HD = TABLE;
+  constexpr ProfileTraits T = profile_traits(K);
+  constexpr int NW = T.waves, BS = NW * 64, KB = T.kb, MB = T.mb;
+  constexpr bool PACKED = T.storage == GramStorage::Packed;
+  constexpr bool TABLE = T.source == GramSource::Table, G64 = T.source == GramSource::SuperTile64;
+  constexpr bool HD = TABLE;  // the packed diagonal stored halved (the notes above pk_store_tile)
   NR_STAMP_INIT();
   uint64_t t_mark = P.stamps && threadIdx.x == 0 ? nr_clock() : 0;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int s_flags[8];
   const int kmax = KB > 0 ? KB : (P.kvec > 0 ? P.kvec : P.k_max);  // LDS vector length
-  const int mmax = KB > 0 ? (MB > 0 ? MB : (KB < 160 ? KB : 160)) : P.m_max;
+  const int mmax = KB > 0 ? MB : P.m_max;
   const int S = (int)P.n_samples;
-  double* part;
-  // Large modules (the full-Gram classes, !PACKED only): the per-wave matvec partials live
-  // in the slot's scratch behind the basis; the workgroup's barriers order
-  // them (one CU, one vector L1).
-  const bool pglob = !PACKED && P.part_global;
-  // packed: one partial array per wave, which also serves as the Ritz checks'
-  // work area (twork, 5 mmax doubles) between matvecs
+  // The per-wave matvec partials. Packed: in LDS, one array per wave, which
+  // also serves as the Ritz checks' work area (twork, 5 mmax doubles) between
+  // matvecs. Full Gram: in the slot's scratch behind the basis; the
+  // workgroup's barriers order them (one CU, one vector L1).
   const int64_t n_part = PACKED ? packed_part_doubles(NW, kmax, mmax) : (int64_t)NW * kmax;
   double* G = P.scratch + (int64_t)blockIdx.x * P.scratch_stride;  // Gram
   const int ld = P.ld;
   double* Q = G + P.gram_doubles;                                  // Lanczos basis
   // FullVectorsInScratch: every vector in the slot's scratch behind the partials
   const bool vglob = !PACKED && P.vec_global;
-  part = nullptr;
+  double* part = nullptr;
   const LzLds L = vglob ? carve_split<NW>(smem, Q + P.basis_doubles + (int64_t)NW * kmax, kmax, mmax)
-                        : carve_lds<NW>(smem, kmax, mmax, pglob ? 0 : n_part, &part, PACKED);
+                        : carve_lds<NW>(smem, kmax, mmax, PACKED ? n_part : 0, &part, PACKED);
   const int tid = threadIdx.x;
   // fp32 copy of the packed Gram for the relaxed Lanczos steps (0: off)
   float* G32 = PACKED && P.g32_off > 0 ? reinterpret_cast<float*>(G + P.g32_off) : nullptr;
-  if (pglob) part = Q + P.basis_doubles;
-  // modules of more than kmax nodes (dual by construction, engine.hip
-  // plan_profile): x_c.u, column means, sums of squares, contributions and the
-  // index set in the slot's scratch
-  double* gnode = Q + P.basis_doubles + (pglob ? (int64_t)NW * kmax : 0);
+  if (!PACKED) part = Q + P.basis_doubles;
+  // modules of more than kmax nodes (dual by construction, plan_profile):
+  // x_c.u, column means, sums of squares, contributions and the index set in
+  // the slot's scratch
+  double* gnode = Q + P.basis_doubles + (PACKED ? 0 : n_part);
   const double* __restrict__ X = P.data;
   const double Sd = (double)S;
 
@@ -2116,49 +2105,37 @@ __device__ __forceinline__ void profile_body(const ProfileParams& P) {
     const int kc = n + 1;
     double g1[1] = {0.0};
     int bad = 0;
-    bool gram_done = false;
-    auto gl = [&](int64_t a) -> double { return G[a]; };
-    if (TABLE || (PACKED && P.fused == 1 && !dual)) {
+    if constexpr (TABLE) {
       // Gram table: the item's network statistics from one 32-byte gather per
       // pair, which also carries G_ij -- the packed Gram is filled here (into
       // a zeroed region: padding and the diagonal blocks' upper parts stay 0)
       // and the matrix-core Gram is skipped. The per-node arrays live in the
       // Lanczos vectors' LDS, idle until the Lanczos phase.
       const GramOut go{G, G32, kc, Sd};
-      {
-        // The fill below writes every lower-triangle entry over kc = k + 1
-        // (pairs, diagonal, ones column); zero only what it never writes: the
-        // diagonal blocks' upper parts, which include the last group's
-        // columns >= kc (its rows all lie in its diagonal block). (Round 3:
-        // zeroing the whole packed region first doubled the item's Gram
-        // stores.)
-        const int ngr = pk_groups(kc);
-        for (int i = tid; i < ngr * 256; i += BS) {
-          const int g = i >> 8, r = 16 * g + ((i >> 4) & 15), c = 16 * g + (i & 15);
-          if (r < c && r < kc) go.put(pk_at(r, c, kc), 0.0);
-        }
-        __syncthreads();
+      // The fill below writes every lower-triangle entry over kc = k + 1
+      // (pairs, diagonal, ones column); zero only what it never writes: the
+      // diagonal blocks' upper parts, which include the last group's columns
+      // >= kc (its rows all lie in its diagonal block). (Round 3: zeroing the
+      // whole packed region first doubled the item's Gram stores.)
+      const int ngr = pk_groups(kc);
+      for (int i = tid; i < ngr * 256; i += BS) {
+        const int g = i >> 8, r = 16 * g + ((i >> 4) & 15), c = 16 * g + (i & 15);
+        if (r < c && r < kc) go.put(pk_at(r, c, kc), 0.0);
       }
-      // (the engine fuses only launches without dual items: k <= S)
+      __syncthreads();
       const NetLds NL = carve_net_over<NW>(L.q, L.red, L.idx, kmax);
-      double gp = 0.0;
-      int bp = 0;
-      net_item<NW, NR_TABLE_PIPE, true, true, NR_TABLE_U, 2, HD>(P.net, m, p_local, off, k, NL, go, &gp, &bp);
-      g1[0] = gp;
-      bad = bp;
-      gram_done = true;
+      net_item<NW, NR_TABLE_PIPE, true, true, NR_TABLE_U, 2>(P.net, m, p_local, off, k, NL, go, g1, &bad);
       for (int64_t i = tid; i < n_part; i += BS) part[i] = 0.0;  // the per-node arrays overlapped them
-    }
-    // ---- Gram [X 1]^T [X 1] on the matrix cores (S x S dual when k > S) ----
-    if (G64) {
+    } else if constexpr (G64) {
+      // ---- Gram [X 1]^T [X 1] on the matrix cores (S x S dual when k > S) ----
       if (dual)
         gram_mfma128<NW, true, kGramDualRows>(X, S, Li.idx, k, P.ones_off, G, G32, g1[0], bad);
       else
         gram_mfma64<NW, false>(X, S, L.idx, k, P.ones_off, G, G32, g1[0], bad);
-    } else if (!TABLE) {
+    } else {
       if (dual)
         gram_mfma_dual<NW, PACKED>(X, S, Li.idx, k, G, G32, ld, g1[0], bad);
-      else if (!gram_done)
+      else
         gram_mfma<NW, PACKED>(X, S, L.idx, k, P.ones_off, G, G32, ld, g1[0], bad);
     }
     if (bad) atomicOr(&s_flags[1], 1);
@@ -2173,7 +2150,7 @@ __device__ __forceinline__ void profile_body(const ProfileParams& P) {
     if (s_flags[1] == 0) {
       if (!dual)
         for (int c = tid; c < k; c += BS)
-          L.colm[c] = (PACKED ? gl(pk_at(k, c, kc)) : G[k + (int64_t)c * ld]) / Sd;
+          L.colm[c] = (PACKED ? G[pk_at(k, c, kc)] : G[k + (int64_t)c * ld]) / Sd;
       bool relax = false;
       auto mv = [&](const double* x, double* out, const double* y) -> double {
         if (!PACKED) return matvec(G, ld, n, x, out, part, kmax, y, L.red);
@@ -2190,7 +2167,7 @@ __device__ __forceinline__ void profile_body(const ProfileParams& P) {
         profile_contrib_dual<NW>(P, k, m, Li, X, S, g1[0]);
       } else {
         profile_contrib<NW>(P, k, m, L, X, S, g1[0], mv, [&](int c) {
-          return PACKED ? (HD ? 2.0 : 1.0) * gl(pk_col(c, kc)) : G[c + (int64_t)c * ld];  // (HD: stored halved)
+          return PACKED ? (HD ? 2.0 : 1.0) * G[pk_col(c, kc)] : G[c + (int64_t)c * ld];  // (HD: stored halved)
         }, gv_rel);
       }
       NR_STAMP(11);  // node contributions
@@ -2203,33 +2180,40 @@ __device__ __forceinline__ void profile_body(const ProfileParams& P) {
   NR_STAMP_FLUSH();
 }
 
-__global__ void __launch_bounds__(NR_BS, 3)
+// A kernel's workgroup size and waves per SIMD, from its description.
+#define NR_PROFILE_BOUNDS(K) __launch_bounds__(64 * profile_traits(K).waves, profile_traits(K).launch_occ)
+static_assert(profile_traits(ProfileKernel::FullGram).waves == NR_WAVES, "matvec (the full Gram) runs on NR_WAVES waves");
+
+__global__ void NR_PROFILE_BOUNDS(ProfileKernel::FullGram)
 module_profile_kernel(ProfileParams P) {
-  profile_body<NR_WAVES, false, 0>(P);
+  profile_body<ProfileKernel::FullGram>(P);
 }
 
-// Packed Gram in the lean 4-wave structure (OCC workgroups per CU).
+// Packed Gram in the lean 4-wave structure, compile-time LDS layout (KB > 0)
+// or runtime. (KB and OCC restate the description: the symbols profiles name.)
 template <int KB, int OCC>
 __global__ void __launch_bounds__(NR_BS, OCC)
 module_profile_packed4_kernel(ProfileParams P) {
-  profile_body<NR_WAVES, true, KB>(P);
+  constexpr ProfileKernel K = KB > 0 ? ProfileKernel::PackedFixed : ProfileKernel::PackedRuntime;
+  static_assert(profile_traits(K).kb == KB && profile_traits(K).launch_occ == OCC, "not profile_traits(K)");
+  profile_body<K>(P);
 }
 
 // Packed modules beyond the compile-time layout (runtime LDS layout, one
 // workgroup per CU): the 64 x 64 super-tile Gram at one wave per SIMD. (The
 // 128 x 128 LDS-staged workgroup tile measured 8% slower on C5 and was
 // removed, profiles/r04/ab7/.)
-__global__ void __launch_bounds__(NR_BS, 1)
+__global__ void NR_PROFILE_BOUNDS(ProfileKernel::PackedBig)
 module_profile_big_kernel(ProfileParams P) {
-  profile_body<NR_WAVES, true, 0, 0, false, true>(P);
+  profile_body<ProfileKernel::PackedBig>(P);
 }
 
-// The Gram-table launches of the packed class (every item fused, k <= S).
+// The Gram-table launches of the packed class (every item from the table, k <= S).
 // (An LDS prefix of the item's Gram and a CU-resident one-workgroup-per-CU
 // version measured equal and 1.8x slower: profiles/r04/ab4/, r04/resident/.)
-__global__ void __launch_bounds__(kTableWaves * 64, 3)
+__global__ void NR_PROFILE_BOUNDS(ProfileKernel::Table)
 module_profile_table_kernel(ProfileParams P) {
-  profile_body<kTableWaves, true, kPackedLayoutK, 0, true>(P);
+  profile_body<ProfileKernel::Table>(P);
 }
 
 // The small class: Lanczos dimension <= kSmallDim (MB = KB = kSmallDim), NW
@@ -2238,9 +2222,10 @@ module_profile_table_kernel(ProfileParams P) {
 // per CU as the LDS holds. (Computing the items' network statistics in the
 // same workgroups measured 1.6x slower on C2, profiles/r04/ab2/.)
 template <int NW>
-__global__ void __launch_bounds__(NW * 64, kSmallOcc)
+__global__ void NR_PROFILE_BOUNDS(ProfileKernel::Small)
 module_profile_small_kernel(ProfileParams P) {
-  profile_body<NW, true, kSmallDim, kSmallDim>(P);
+  static_assert(NW == profile_traits(ProfileKernel::Small).waves, "not the kernel profile_traits describes");
+  profile_body<ProfileKernel::Small>(P);
 }
 
 // ---------------------------------------------------------------------------
@@ -2508,7 +2493,7 @@ __device__ __forceinline__ bool wave_start_column(const nr_f64x4 (&T)[kWaveTiles
   return ok;
 }
 
-__global__ void __launch_bounds__(64, 1)
+__global__ void NR_PROFILE_BOUNDS(ProfileKernel::Wave)
 module_profile_wave_kernel(ProfileParams P) {
   constexpr int KB = kWaveVec, MB = kWaveVec;
   NR_STAMP_INIT();
@@ -2840,29 +2825,18 @@ hipError_t launch_net(const NetParams& P0, int64_t n_items, hipStream_t st) {
 
 hipError_t launch_profile(const ProfileParams& P, const ProfilePlan& plan, hipStream_t st) {
   const dim3 g((unsigned)plan.slots), b((unsigned)plan.block);
+#define NR_PROFILE_LAUNCH(K, ...) \
+  case ProfileKernel::K: hipLaunchKernelGGL((__VA_ARGS__), g, b, plan.lds, st, P); break
   switch (plan.kernel) {
-    case ProfileKernel::FullGram:
-      hipLaunchKernelGGL(module_profile_kernel, g, b, plan.lds, st, P);
-      break;
-    case ProfileKernel::PackedFixed:
-      hipLaunchKernelGGL((module_profile_packed4_kernel<kPackedLayoutK, 3>), g, b, plan.lds, st, P);
-      break;
-    case ProfileKernel::PackedRuntime:
-      hipLaunchKernelGGL((module_profile_packed4_kernel<0, 2>), g, b, plan.lds, st, P);
-      break;
-    case ProfileKernel::PackedBig:
-      hipLaunchKernelGGL(module_profile_big_kernel, g, b, plan.lds, st, P);
-      break;
-    case ProfileKernel::Table:
-      hipLaunchKernelGGL(module_profile_table_kernel, g, b, plan.lds, st, P);
-      break;
-    case ProfileKernel::Small:
-      hipLaunchKernelGGL((module_profile_small_kernel<kSmallWaves>), g, b, plan.lds, st, P);
-      break;
-    case ProfileKernel::Wave:
-      hipLaunchKernelGGL(module_profile_wave_kernel, g, b, plan.lds, st, P);
-      break;
+    NR_PROFILE_LAUNCH(FullGram, module_profile_kernel);
+    NR_PROFILE_LAUNCH(PackedFixed, module_profile_packed4_kernel<kPackedLayoutK, 3>);
+    NR_PROFILE_LAUNCH(PackedRuntime, module_profile_packed4_kernel<0, 2>);
+    NR_PROFILE_LAUNCH(PackedBig, module_profile_big_kernel);
+    NR_PROFILE_LAUNCH(Table, module_profile_table_kernel);
+    NR_PROFILE_LAUNCH(Small, module_profile_small_kernel<kSmallWaves>);
+    NR_PROFILE_LAUNCH(Wave, module_profile_wave_kernel);
   }
+#undef NR_PROFILE_LAUNCH
   return hipGetLastError();
 }
 

@@ -26,9 +26,6 @@ enum class ProfileClass {
   FullVectorsInScratch,   // min(k, S) beyond those as well: every Lanczos vector and the index set
                           // in scratch, no size limit but device memory ("variant 6")
 };
-// (A full Gram with the partials in LDS, once "variant 0", needs at least the
-// packed layout's LDS -- 10 k + 12 m >= 6 k + max(4 k, 5 m) + 7 m doubles -- so
-// no shape ever planned it; the kernel's part_global == 0 path is left over.)
 
 enum class ProfileKernel {
   FullGram,       // module_profile_kernel
@@ -39,6 +36,52 @@ enum class ProfileKernel {
   Small,          // module_profile_small_kernel<kSmallWaves>
   Wave,           // module_profile_wave_kernel
 };
+
+constexpr int kPackedLayoutK = 320;  // modules of the packed kernel's compile-time LDS layout
+constexpr int kPackedLayoutM = kPackedLayoutK < 160 ? kPackedLayoutK : 160;  // its Lanczos basis columns
+// The small class: several items per CU in flight instead of three 4-wave
+// items; per-node arrays of modules longer than kSmallDim in the slot's scratch.
+constexpr int kSmallDim = 112;
+constexpr int kSmallWaves = 2;  // (one wave per item measured slower: profiles/r03/small_class/)
+// The wave class (round 5): the item's whole Gram in one wave's registers (kernels.hip).
+constexpr int kWaveBlocks = 7;                // 16-row blocks of the Gram's side (<= 112)
+constexpr int kWaveVec = 16 * kWaveBlocks;     // LDS vector length and Lanczos basis columns
+constexpr int kWaveDim = kWaveVec - 1;         // the side is the dimension plus the ones column
+constexpr int kTableWaves = 4;  // (2 waves x 5 per CU measured 13% slower, profiles/r03/table_waves/)
+
+enum class GramStorage { Full, Packed };  // ld x ld, or the packed lower triangle (kernels.hip, pk_at)
+// Who fills an item's Gram. A kernel compiles one: with two, the compiler
+// merges their MFMA blocks and spills around them.
+enum class GramSource {
+  MatrixCore,   // gram_mfma / gram_mfma_dual: 32 x 32 super-tiles
+  SuperTile64,  // gram_mfma64 / gram_mfma128: 64-row super-tiles per wave, one workgroup per CU
+  Table,        // the table's gathers, with the item's network statistics: no dual items, diagonal halved
+};
+
+// What a kernel is compiled as: the planner sizes its launches from this, and
+// the kernel's body and __launch_bounds__ are instantiated from it.
+struct ProfileTraits {
+  int waves;       // per workgroup
+  int launch_occ;  // second __launch_bounds__ argument: waves per SIMD the registers must allow
+  int cu_cap;      // workgroups per CU the planner asks for at most
+  int kb, mb;      // compile-time LDS layout: vector length, basis columns (0: the plan's kvec, m)
+  GramStorage storage;
+  GramSource source;  // (the wave kernel has its own body: the Gram in registers)
+};
+constexpr ProfileTraits profile_traits(ProfileKernel k) {
+  constexpr auto PK = GramStorage::Packed;
+  constexpr auto MC = GramSource::MatrixCore;
+  switch (k) {
+    case ProfileKernel::FullGram: return {4, 3, 1, 0, 0, GramStorage::Full, MC};
+    case ProfileKernel::PackedFixed: return {4, 3, 3, kPackedLayoutK, kPackedLayoutM, PK, MC};
+    case ProfileKernel::PackedRuntime: return {4, 2, 3, 0, 0, PK, MC};
+    case ProfileKernel::PackedBig: return {4, 1, 1, 0, 0, PK, GramSource::SuperTile64};
+    case ProfileKernel::Table: return {kTableWaves, 3, 3, kPackedLayoutK, kPackedLayoutM, PK, GramSource::Table};
+    case ProfileKernel::Small: return {kSmallWaves, 3, 12 / kSmallWaves, kSmallDim, kSmallDim, PK, MC};  // 12 waves per CU
+    case ProfileKernel::Wave: break;
+  }
+  return {1, 1, 4, kWaveVec, kWaveVec, PK, MC};
+}
 
 struct ProfilePlan {
   ProfileClass cls = ProfileClass::Packed;
@@ -56,8 +99,7 @@ struct ProfilePlan {
   // [per-node arrays of big modules], [Lanczos vectors + index set], [fp32 Gram copy]
   int64_t gram_doubles = 0, basis_doubles = 0, stride = 0;
   int64_t g32_off = 0;       // fp32 copy of the packed Gram (relaxed Lanczos steps), 0: none
-  bool part_global = false;  // the matvec partials (4 x kvec) behind the basis
-  bool vec_global = false;   // the Lanczos vectors and index set behind them
+  bool vec_global = false;   // the Lanczos vectors and index set behind the partials
 };
 
 // Plans a launch of n_items items of modules of at most k_max nodes over

@@ -4,7 +4,8 @@
 //                              for every kernel class's parameters and holds the
 //                              result against the byte formulas and the planner
 //   profile_plan_check plans   reads "k_max n_samples n_items [data_doubles]"
-//                              lines, prints each plan (256 CUs)
+//                              lines, prints each plan (256 CUs) and holds its
+//                              workgroup against the kernel's description
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -105,8 +106,10 @@ size_t check_carve(const char* what, int kvec, int mmax, int64_t extra, bool two
   return bytes;
 }
 
+constexpr int kFullWaves = profile_traits(ProfileKernel::FullGram).waves;  // and the packed 4-wave kernels'
+
 size_t check_split(int kvec, int mmax, std::vector<double>& gbuf) {
-  constexpr int NW = NR_WAVES;
+  constexpr int NW = kFullWaves;
   const char* what = "all in scratch";
   const size_t bytes = carve_split_bytes(NW, mmax);
   CHECK(bytes <= kLdsBudget, "%s: %zu bytes (mmax %d)", what, bytes, mmax);
@@ -134,48 +137,59 @@ size_t check_split(int kvec, int mmax, std::vector<double>& gbuf) {
   return bytes;
 }
 
-// The carve-out a planned launch's kernel makes (the arguments of
-// profile_body and the wave kernel in kernels.hip), against plan.lds.
+// The carve-out kernel K makes of a planned launch (profile_body and the wave
+// kernel in kernels.hip), from the description the kernel is compiled from.
+template <ProfileKernel K>
+size_t carve_as(const ProfilePlan& q, std::vector<double>& gbuf) {
+  constexpr ProfileTraits T = profile_traits(K);
+  const char* what = profile_kernel_name(K);
+  const int kvec = T.kb > 0 ? T.kb : q.kvec, m = T.kb > 0 ? T.mb : q.m;
+  if (K == ProfileKernel::Wave) return check_carve<T.waves>(what, kvec, m, 3 * kvec, false);
+  if (T.storage == GramStorage::Packed)
+    return check_carve<T.waves>(what, kvec, m, packed_part_doubles(T.waves, kvec, m), true);
+  return q.vec_global ? check_split(kvec, m, gbuf) : check_carve<T.waves>(what, kvec, m, 0, false);
+}
+
+size_t carve_planned(const ProfilePlan& q, std::vector<double>& gbuf) {
+  switch (q.kernel) {
+    case ProfileKernel::Wave: return carve_as<ProfileKernel::Wave>(q, gbuf);
+    case ProfileKernel::Small: return carve_as<ProfileKernel::Small>(q, gbuf);
+    case ProfileKernel::Table: return carve_as<ProfileKernel::Table>(q, gbuf);
+    case ProfileKernel::PackedFixed: return carve_as<ProfileKernel::PackedFixed>(q, gbuf);
+    case ProfileKernel::PackedRuntime: return carve_as<ProfileKernel::PackedRuntime>(q, gbuf);
+    case ProfileKernel::PackedBig: return carve_as<ProfileKernel::PackedBig>(q, gbuf);
+    case ProfileKernel::FullGram: return carve_as<ProfileKernel::FullGram>(q, gbuf);
+  }
+  return 0;
+}
+
+// A plan launches its kernel on the workgroup the kernel is compiled for, at
+// no more workgroups per CU than the kernel's cap.
+void check_shape(const ProfilePlan& q) {
+  const ProfileTraits T = profile_traits(q.kernel);
+  CHECK(q.block == 64 * T.waves, "%s: block %d, %d waves", profile_kernel_name(q.kernel), q.block, T.waves);
+  CHECK(q.per_cu >= 1 && q.per_cu <= T.cu_cap, "%s: per_cu %d, cap %d", profile_kernel_name(q.kernel), q.per_cu,
+        T.cu_cap);
+}
+
 void check_plan(int k_max, int n_samples) {
   ProfilePlan p;
   if (!plan_profile(1000000, k_max, n_samples, 0, 256, &p)) {
     CHECK(false, "no plan for k_max %d, n_samples %d", k_max, n_samples);
     return;
   }
-  constexpr int LK = kPackedLayoutK, LM = LK < 160 ? LK : 160;
   std::vector<double> gbuf;
-  size_t carved = 0;
-  auto plan_one = [&](const ProfilePlan& q) {
-    const char* what = profile_kernel_name(q.kernel);
-    switch (q.kernel) {
-      case ProfileKernel::Wave:
-        return check_carve<1>(what, kWaveVec, kWaveVec, 3 * kWaveVec, false);
-      case ProfileKernel::Small:
-        return check_carve<kSmallWaves>(what, kSmallDim, kSmallDim,
-                                        packed_part_doubles(kSmallWaves, kSmallDim, kSmallDim), true);
-      case ProfileKernel::Table:
-        return check_carve<kTableWaves>(what, LK, LM, packed_part_doubles(kTableWaves, LK, LM), true);
-      case ProfileKernel::PackedFixed:
-        return check_carve<NR_WAVES>(what, LK, LM, packed_part_doubles(NR_WAVES, LK, LM), true);
-      case ProfileKernel::PackedRuntime:
-      case ProfileKernel::PackedBig:
-        return check_carve<NR_WAVES>(what, q.kvec, q.m, packed_part_doubles(NR_WAVES, q.kvec, q.m), true);
-      case ProfileKernel::FullGram:
-        CHECK(q.part_global, "full Gram with the partials in LDS planned (k_max %d, n_samples %d)", k_max, n_samples);
-        return q.vec_global ? check_split(q.kvec, q.m, gbuf) : check_carve<NR_WAVES>(what, q.kvec, q.m, 0, false);
-    }
-    return (size_t)0;
-  };
-  carved = plan_one(p);
+  size_t carved = carve_planned(p, gbuf);
   CHECK(carved == p.lds, "%s: plan.lds %zu, carved %zu (k_max %d, n_samples %d)", profile_kernel_name(p.kernel), p.lds,
         carved, k_max, n_samples);
-  CHECK(p.kernel != ProfileKernel::PackedFixed || k_max <= LK, "compile-time layout for k_max %d", k_max);
+  CHECK(p.kernel != ProfileKernel::PackedFixed || k_max <= kPackedLayoutK, "compile-time layout for k_max %d", k_max);
+  check_shape(p);
   if (profile_takes_table(p, k_max, n_samples)) {
     profile_use_table(&p);
-    carved = plan_one(p);
+    carved = carve_planned(p, gbuf);
     CHECK(carved == p.lds, "table: plan.lds %zu, carved %zu (k_max %d, n_samples %d)", p.lds, carved, k_max,
           n_samples);
-    CHECK(p.block == 64 * kTableWaves, "table: block %d", p.block);
+    check_shape(p);
   }
 }
 
@@ -184,12 +198,12 @@ int carve_mode() {
   for (const int m : {113, 160, 320}) {
     int n = 0;
     for (int kvec = kPackedLayoutK + 1;
-         carve_lds_bytes(NR_WAVES, kvec, m, packed_part_doubles(NR_WAVES, kvec, m), true) <= kLdsBudget; ++kvec, ++n)
-      check_carve<NR_WAVES>("packed, runtime layout", kvec, m, packed_part_doubles(NR_WAVES, kvec, m), true);
+         carve_lds_bytes(kFullWaves, kvec, m, packed_part_doubles(kFullWaves, kvec, m), true) <= kLdsBudget; ++kvec, ++n)
+      check_carve<kFullWaves>("packed, runtime layout", kvec, m, packed_part_doubles(kFullWaves, kvec, m), true);
     CHECK(n > 1000, "packed sweep too short: %d", n);
     n = 0;
-    for (int kvec = 1; carve_lds_bytes(NR_WAVES, kvec, m, 0, false) <= kLdsBudget; ++kvec, ++n)
-      check_carve<NR_WAVES>("full Gram, partials in scratch", kvec, m, 0, false);
+    for (int kvec = 1; carve_lds_bytes(kFullWaves, kvec, m, 0, false) <= kLdsBudget; ++kvec, ++n)
+      check_carve<kFullWaves>("full Gram, partials in scratch", kvec, m, 0, false);
     CHECK(n > 2000, "full-Gram sweep too short: %d", n);
     std::vector<double> gbuf;
     for (int kvec = 1; kvec <= 20000; kvec += kvec < 3000 ? 1 : 997) check_split(kvec, m, gbuf);
@@ -214,13 +228,17 @@ int plans_mode() {
            "g32_off=%lld part_global=%d vec_global=%d takes_table=%d\n",
            k, S, items, data, ok ? 0 : 1, profile_class_name(p.cls), profile_kernel_name(p.kernel), p.block, p.lds,
            p.per_cu, p.slots, p.k_gram, p.ld, p.m, p.kvec, (int)p.big, (long long)p.gram_doubles,
-           (long long)p.basis_doubles, (long long)p.stride, (long long)p.g32_off, (int)p.part_global,
+           (long long)p.basis_doubles, (long long)p.stride, (long long)p.g32_off,
+           (int)(ok && p.kernel == ProfileKernel::FullGram),  // (the full Gram's partials: always in scratch)
            (int)p.vec_global, (int)(ok && profile_takes_table(p, (int)k, S)));
+    if (ok) check_shape(p);
   }
   ProfilePlan t;
   profile_use_table(&t);
+  check_shape(t);
   printf("table_kernel=%s block=%d lds=%zu\n", profile_kernel_name(t.kernel), t.block, t.lds);
-  return 0;
+  if (g_failed) fprintf(stderr, "%d checks failed\n", g_failed);
+  return g_failed ? 1 : 0;
 }
 
 }  // namespace
