@@ -90,6 +90,23 @@ int nr_set_dataset_ex(nr_ctx* ctx, const double* corr, const double* net,
 #define NR_NET_UNSIGNED 0
 #define NR_NET_SIGNED 1
 #define NR_NET_SIGNED_HYBRID 2
+/* OR-ed onto one of the three: the resident net becomes the topological
+ * overlap matrix of that adjacency (WGCNA's unsigned TOM, TOMDenom = "min").
+ * With a = net as above but a zero diagonal:
+ *   k_i  = sum_u a_ui
+ *   L_ij = sum_u a_iu a_uj
+ *   t_ij = (L_ij + a_ij) / (min(k_i, k_j) + 1 - a_ij)   for i != j,  t_ii = 1
+ * NaN propagates (a constant column makes every off-diagonal t NaN; the
+ * diagonal stays 1); the denominator is >= 1. corr is what it is without the
+ * flag, bit for bit, and t is stored at (i, j) and (j, i) from the same bits.
+ * The order of work on the context's stream: the build as above, one pass
+ * that extracts a and sums its columns in a fixed order (no atomics), then a
+ * second lower-triangle SYRK with K = n_nodes on the fp64 matrix cores. It
+ * needs 8 n (n + 2) + 8 n bytes of device scratch for the call (n = n_nodes),
+ * freed before the call returns; when that allocation fails the call returns
+ * NR_ERR_OOM and leaves no dataset resident. Any other net_type value stays
+ * NR_ERR_INVALID. */
+#define NR_NET_TOM 0x10
 int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples,
                              int where, int flags, int net_type, double beta);
 /* Device time in ms (HIP events on the context's stream) of the kernel that
@@ -97,6 +114,11 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
  * any other way. A copy (nr_copy_dataset, nr_broadcast_dataset) reports the
  * figure of the dataset it was copied from. */
 int nr_netbuild_ms(nr_ctx* ctx, double* ms);
+/* Device time in ms of the NR_NET_TOM step behind that kernel (extract,
+ * degrees and the TOM kernel together; nr_netbuild_ms does not include it);
+ * 0 for a dataset built without NR_NET_TOM or made any other way. A copy
+ * reports its source's figure. */
+int nr_tom_ms(nr_ctx* ctx, double* ms);
 /* The resident corr and net (n_nodes x n_nodes each, column-major) to host
  * arrays; either may be NULL. Works for a dataset made by any of the
  * set-dataset calls, before or after the Gram table is built: the pairs are
@@ -437,7 +459,8 @@ int netrep_PermutationProcedureFiles(const netrep_disc_props* disc_props, const 
 /* PermutationProcedure with the test dataset given as its data matrix alone
  * (nr_set_dataset_from_data on GPU 0: t_data is uploaded, scaled there when
  * scale_data != 0, and the correlation and network are built in HBM from it
- * by net_type (NR_NET_*) and beta; no n x n host matrix exists or crosses
+ * by net_type (NR_NET_*, with NR_NET_TOM OR-ed on: the network is the
+ * topological overlap of that adjacency) and beta; no n x n host matrix exists or crosses
  * PCIe). Built matrices that are not all finite -- a constant column, for
  * which R's cor gives NA -- return NR_ERR_NONFINITE with CheckFinite's
  * message before any permutation runs (the reference stops such input in
@@ -454,7 +477,8 @@ int netrep_PermutationProcedureFromData(
 
 /* The same build, copied back: corr_out and net_out (n_nodes x n_nodes each,
  * either may be NULL) for callers who still need host matrices, e.g. for the
- * discovery-side calls. Non-finite results are returned as they are. */
+ * discovery-side calls. With NR_NET_TOM in net_type, net_out is the
+ * topological overlap matrix. Non-finite results are returned as they are. */
 int netrep_BuildNetwork(const double* data, int32_t scale_data, int32_t net_type, double beta,
                         int64_t n_samples, int64_t n_nodes, double* corr_out, double* net_out);
 

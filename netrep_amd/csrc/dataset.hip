@@ -337,7 +337,9 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
   if (!data) return fail(ctx, NR_ERR_INVALID, "data missing");
   if (n_nodes < 1 || n_samples < 2) return fail(ctx, NR_ERR_INVALID, "data needs n_nodes >= 1 and n_samples >= 2");
   if (where != NR_HOST && where != NR_DEVICE) return fail(ctx, NR_ERR_INVALID, "where must be NR_HOST or NR_DEVICE");
-  if (net_type != NR_NET_UNSIGNED && net_type != NR_NET_SIGNED && net_type != NR_NET_SIGNED_HYBRID)
+  const int base_type = net_type & ~NR_NET_TOM;
+  const bool tom = (net_type & NR_NET_TOM) != 0;
+  if (base_type != NR_NET_UNSIGNED && base_type != NR_NET_SIGNED && base_type != NR_NET_SIGNED_HYBRID)
     return fail(ctx, NR_ERR_INVALID, "unknown network type");
   if (!std::isfinite(beta) || beta <= 0.0) return fail(ctx, NR_ERR_INVALID, "beta must be finite and > 0");
   if (n_nodes > (int64_t)INT32_MAX) return fail(ctx, NR_ERR_UNSUPPORTED, "n_nodes exceeds 2^31-1");
@@ -352,24 +354,53 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
     int rc = load_data_block(ctx, ds, n_nodes, n_samples, (flags & NR_SCALE_DATA) != 0,
                              [&](double* dst) { return put_data(ctx, data, n_samples * n_nodes, where, dst); });
     if (rc) return rc;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipError_t e = hipEventCreate(&ev[0]);
-    if (e == hipSuccess) e = hipEventCreate(&ev[1]);
-    float ms = 0.f;
+    // The TOM scratch (kernels.h, launch_tom): the plain adjacency A,
+    // column-major, n rows x (n + 2) columns, and the n degrees behind it:
+    // 8 n (n + 2) + 8 n bytes. Padding rule (the data block's): columns
+    // 0 .. n - 1 hold values (zero diagonal); column n + 1 is all zeros and is
+    // what the SYRK main loop reads for every panel column past n; column n is
+    // never read and is zeroed too. tom_extract_kernel writes all n + 2
+    // columns. The scratch lives for this call only (freed on every path).
+    struct Scratch {
+      double* p = nullptr;
+      ~Scratch() {
+        if (p) (void)hipFree(p);
+      }
+    } tom_scratch;
+    if (tom) {
+      const size_t tom_bytes = nr::tom_scratch_bytes(n_nodes);
+      if (hipMalloc((void**)&tom_scratch.p, tom_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        tom_scratch.p = nullptr;
+        return fail(ctx, NR_ERR_OOM,
+                    "from-data dataset: allocation of the " + std::to_string(tom_bytes) + "-byte (" +
+                        std::to_string(tom_bytes >> 20) + " MiB) TOM scratch failed (8 n (n + 2) + 8 n bytes)");
+      }
+    }
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (hipEvent_t& x : ev)
+      if (e == hipSuccess) e = hipEventCreate(&x);
+    float ms = 0.f, ms_tom = 0.f;
+    // one flag word for both epilogues: netbuild's, then the TOM's on top
     if (e == hipSuccess)
       rc = read_flags(ctx, ds, "from-data build", [&](int* flag) {
         hipError_t p = hipEventRecord(ev[0], ctx->stream);
         if (p == hipSuccess)
-          p = nr::launch_netbuild(ds.d_data, n_samples, n_nodes, ds.d_pairs, net_type, beta, flag, ctx->stream);
+          p = nr::launch_netbuild(ds.d_data, n_samples, n_nodes, ds.d_pairs, base_type, beta, flag, ctx->stream);
         if (p == hipSuccess) p = hipEventRecord(ev[1], ctx->stream);
+        if (p == hipSuccess && tom) p = nr::launch_tom(n_nodes, ds.d_pairs, tom_scratch.p, flag, ctx->stream);
+        if (p == hipSuccess) p = hipEventRecord(ev[2], ctx->stream);
         return p;
       });
     if (e == hipSuccess && !rc) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
+    if (e == hipSuccess && !rc && tom) e = hipEventElapsedTime(&ms_tom, ev[1], ev[2]);
     for (hipEvent_t x : ev)
       if (x) (void)hipEventDestroy(x);
     if (rc) return rc;
     if (e != hipSuccess) return hip_fail(ctx, e, "from-data build");
     ds.netbuild_ms = (double)ms;
+    ds.tom_ms = (double)ms_tom;
     ds.symmetric = 1;  // every tile is stored and mirrored from the same bits
     ds.n_nodes = n_nodes;
     ds.n_samples = n_samples;
@@ -636,6 +667,12 @@ int nr_gram_table_ms(nr_ctx* ctx, double* ms) {
 int nr_netbuild_ms(nr_ctx* ctx, double* ms) {
   if (!ctx || !ms) return NR_ERR_INVALID;
   *ms = ctx->ds.d_pairs ? ctx->ds.netbuild_ms : 0.0;
+  return NR_OK;
+}
+
+int nr_tom_ms(nr_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return NR_ERR_INVALID;
+  *ms = ctx->ds.d_pairs ? ctx->ds.tom_ms : 0.0;
   return NR_OK;
 }
 

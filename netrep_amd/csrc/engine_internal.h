@@ -32,6 +32,7 @@ struct Dataset {
   int corr_finite = 0, net_finite = 0;  // CheckFinite of the resident matrices
   double table_ms = 0.0;         // wall time of the last Gram-table build
   double netbuild_ms = 0.0;      // device time of the from-data build of the matrices (0: not built from data)
+  double tom_ms = 0.0;           // device time of the TOM step behind it (0: built without NR_NET_TOM)
 };
 
 struct nr_ctx {

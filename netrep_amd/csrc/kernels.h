@@ -182,6 +182,17 @@ hipError_t launch_symmetry(const double2* a, int64_t n, int* asym, hipStream_t s
 constexpr int kNetbuildTile = 64;
 hipError_t launch_netbuild(const double* X, int64_t S, int64_t n, double2* pairs, int net_type, double beta,
                            int* flags, hipStream_t st);
+// The topological overlap of a from-data network (NR_NET_TOM), in place: the
+// .y of every pair becomes t_ij = (sum_u a_iu a_uj + a_ij) / (min(k_i, k_j) +
+// 1 - a_ij), a the .y with a zero diagonal, k its column sums, t_ii = 1; the
+// .x keeps its bits. scratch: tom_scratch_bytes(n) bytes, the plain matrix A
+// (n rows, n + 2 columns, column-major: a with a zero diagonal in columns
+// 0 .. n - 1, columns n and n + 1 zero -- the SYRK main loop reads column
+// n + 1 for every panel column past n) and, behind it, k[n]. Two launches:
+// extract + degrees, then the same tile SYRK as launch_netbuild with K = n.
+// flags |= 4 for a non-finite t.
+size_t tom_scratch_bytes(int64_t n);
+hipError_t launch_tom(int64_t n, double2* pairs, double* scratch, int* flags, hipStream_t st);
 // corr[e], net[e] (either may be NULL) = elements [first, first + len) of a
 // pair array in layout es (1, or 2: the Gram table).
 hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,

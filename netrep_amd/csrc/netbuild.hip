@@ -140,6 +140,47 @@ __device__ __forceinline__ void nb_multiply(const double* pA, const double* pB, 
   }
 }
 
+// acc = this wave's quadrant of tile (I, J) of X^T X, X an S x (n + 2)
+// column-major block whose column n + 1, at offset zero_col, is zero (columns
+// past n read it): whole chunks, the next chunk's loads in flight while this
+// one is multiplied; the last, partial chunk (its own code, so that its waits
+// never sit in the whole chunks' path) after them. The panels are free on
+// return. Shared by netbuild_kernel (X the data block) and tom_kernel (X the
+// adjacency scratch, S = n).
+__device__ __forceinline__ void nb_syrk_tile(const double* __restrict__ X, int64_t S, int64_t n, int64_t zero_col,
+                                             int64_t I, int64_t J, double* pA, double* pB, int wr, int wc, int i16,
+                                             int kk, nb_f64x4 (&acc)[2][2]) {
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) acc[a][b] = nb_f64x4{0.0, 0.0, 0.0, 0.0};
+
+  int64_t col_a[4], col_b[4];  // offsets of this thread's panel columns in X
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int64_t ca = I * kNbTile + (threadIdx.x >> 4) + 16 * p, cb = J * kNbTile + (threadIdx.x >> 4) + 16 * p;
+    col_a[p] = ca < n ? ca * S : zero_col;
+    col_b[p] = cb < n ? cb * S : zero_col;
+  }
+  const int64_t s_full = S / kNbChunk * kNbChunk;
+  NbFetch f;
+  if (s_full > 0) nb_fetch<true>(X, S, col_a, col_b, 0, f);
+  for (int64_t s0 = 0; s0 < s_full; s0 += kNbChunk) {
+    nb_to_lds(pA, pB, f);
+    __syncthreads();
+    if (s0 + kNbChunk < s_full) nb_fetch<true>(X, S, col_a, col_b, s0 + kNbChunk, f);
+    nb_multiply(pA, pB, wr, wc, i16, kk, acc);
+    __syncthreads();  // the panels are free (for the next chunk, or the output image)
+  }
+  if (s_full < S) {
+    nb_fetch<false>(X, S, col_a, col_b, s_full, f);
+    nb_to_lds(pA, pB, f);
+    __syncthreads();
+    nb_multiply(pA, pB, wr, wc, i16, kk, acc);
+    __syncthreads();
+  }
+}
+
 __global__ void __launch_bounds__(256, 2)
 netbuild_kernel(const double* __restrict__ X, int64_t S, int64_t n, double2* __restrict__ pairs, int net_type,
                 double beta, int* __restrict__ flags) {
@@ -164,38 +205,7 @@ netbuild_kernel(const double* __restrict__ X, int64_t S, int64_t n, double2* __r
     const bool diag = I == J;
 
     nb_f64x4 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) acc[a][b] = nb_f64x4{0.0, 0.0, 0.0, 0.0};
-
-    int64_t col_a[4], col_b[4];  // offsets of this thread's panel columns in X
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int64_t ca = I * kNbTile + (threadIdx.x >> 4) + 16 * p, cb = J * kNbTile + (threadIdx.x >> 4) + 16 * p;
-      col_a[p] = ca < n ? ca * S : zero_col;
-      col_b[p] = cb < n ? cb * S : zero_col;
-    }
-    // whole chunks: the next chunk's loads are in flight while this one is
-    // multiplied; the last, partial chunk (its own code, so that its waits
-    // never sit in the whole chunks' path) after them
-    const int64_t s_full = S / kNbChunk * kNbChunk;
-    NbFetch f;
-    if (s_full > 0) nb_fetch<true>(X, S, col_a, col_b, 0, f);
-    for (int64_t s0 = 0; s0 < s_full; s0 += kNbChunk) {
-      nb_to_lds(pA, pB, f);
-      __syncthreads();
-      if (s0 + kNbChunk < s_full) nb_fetch<true>(X, S, col_a, col_b, s0 + kNbChunk, f);
-      nb_multiply(pA, pB, wr, wc, i16, kk, acc);
-      __syncthreads();  // the panels are free (for the next chunk, or the output image)
-    }
-    if (s_full < S) {
-      nb_fetch<false>(X, S, col_a, col_b, s_full, f);
-      nb_to_lds(pA, pB, f);
-      __syncthreads();
-      nb_multiply(pA, pB, wr, wc, i16, kk, acc);
-      __syncthreads();
-    }
+    nb_syrk_tile(X, S, n, zero_col, I, J, pA, pB, wr, wc, i16, kk, acc);
 
     // Epilogue, one half of the tile's columns (held by the waves wc == h) at
     // a time: g into stage_g[j][i]; every thread turns 8 elements into {c, w}
@@ -247,6 +257,137 @@ netbuild_kernel(const double* __restrict__ X, int64_t S, int64_t n, double2* __r
   if (bad && lane == 0) atomicOr(flags, bad);
 }
 
+// ---- topological overlap (NR_NET_TOM) ---------------------------------------
+//
+// The TOM scratch matrix A: the adjacency (the pairs' .y) with a zero
+// diagonal, column-major, n rows and n + 2 columns, so that tom_kernel can
+// hand it to the SYRK main loop as "X with S = n". Padding rule (the data
+// block's, restated): columns 0 .. n - 1 hold values; column n + 1 is all
+// zeros and is what every panel column past n reads; column n (the data
+// block's ones column) is never read by the main loop and is zeroed too, so
+// that no byte of the scratch is left undefined.
+//
+// tom_extract_kernel: one workgroup per column j (grid-stride): A(:, j) from
+// the pairs, and the degree k_j = sum_i A(i, j) in one fixed order: thread t
+// adds rows t, t + 256, ... in sequence, then a fixed LDS tree over the 256
+// partial sums. No atomics: k does not depend on scheduling.
+__global__ void __launch_bounds__(256)
+tom_extract_kernel(const double2* __restrict__ pairs, int64_t n, double* __restrict__ A, double* __restrict__ k) {
+  __shared__ double part[256];
+  for (int64_t j = blockIdx.x; j < n + 2; j += gridDim.x) {
+    double* const col = A + j * n;
+    if (j >= n) {  // the two padding columns
+      for (int64_t i = threadIdx.x; i < n; i += 256) col[i] = 0.0;
+      continue;
+    }
+    double sum = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+      const double a = i == j ? 0.0 : pairs[i + j * n].y;
+      col[i] = a;
+      sum += a;
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) k[j] = part[0];
+    __syncthreads();  // part is free for the next column
+  }
+}
+
+// t_ij of WGCNA's unsigned TOM (TOMDenom = "min") from L_ij = sum_u a_iu a_uj,
+// a_ij and the two degrees. The minimum is two selects that keep a NaN of
+// either degree (fmin would drop it); the denominator is >= 1.
+__device__ __forceinline__ double tom_value(double L, double a, double ki, double kj) {
+  double m = ki < kj ? ki : kj;  // kj where kj is NaN
+  m = ki == ki ? m : ki;         // ki where ki is NaN
+  return (L + a) / (m + 1.0 - a);
+}
+
+// tom_kernel: the same lower-triangle SYRK as netbuild_kernel, over A with
+// K = n (main loop: nb_syrk_tile, which reads A only, never the pairs), and
+// its own epilogue: t_ij from L, a_ij (read from A), k_i and k_j, 1 on the
+// diagonal; stored into the .y of pair (i, j) and -- the same bits -- of
+// (j, i) as 8-byte stores, so the .x (corr) keeps its bits. A tile reads and
+// writes only its own (i, j) and (j, i), so the update is in place. flags
+// |= 4 for a non-finite t.
+__global__ void __launch_bounds__(256, 2)
+tom_kernel(const double* __restrict__ A, const double* __restrict__ k, int64_t n, double2* __restrict__ pairs,
+           int* __restrict__ flags) {
+  __shared__ __attribute__((aligned(16))) double lds[kNbPanelDoubles];
+  double* const pA = lds;
+  double* const pB = lds + kNbTile * kNbLd;
+  double* const stage_t = lds;  // [32 columns j][kNbOutLd rows i]: L, then t in place
+  double* const net = reinterpret_cast<double*>(pairs) + 1;  // net[2 e]: the .y of pair e
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i16 = lane & 15, kk = lane >> 4;
+  const int wr = wave & 1, wc = wave >> 1;
+  const int64_t nT = (n + kNbTile - 1) / kNbTile;
+  const int64_t n_tiles = nT * (nT + 1) / 2;
+  const int64_t zero_col = (n + 1) * n;  // A's second padding column
+  int bad = 0;
+
+  for (int64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    int64_t I, J;
+    tile_of(t, I, J);
+    const bool diag = I == J;
+
+    nb_f64x4 acc[2][2];
+    nb_syrk_tile(A, n, n, zero_col, I, J, pA, pB, wr, wc, i16, kk, acc);
+
+    for (int h = 0; h < 2; ++h) {
+      if (wc == h) {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+          for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              stage_t[(16 * b + i16) * kNbOutLd + 32 * wr + 16 * a + kk + 4 * r] = acc[a][b][r];
+      }
+      __syncthreads();
+      // every thread turns its own 8 elements of L into t in place
+      const int64_t gi = I * kNbTile + lane;
+      const double ki = gi < n ? k[gi] : 0.0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int jl = wave + 4 * q;
+        const int64_t gj = J * kNbTile + 32 * h + jl;
+        const bool in = gi < n && gj < n;
+        const double a = in ? A[gi + gj * n] : 0.0;
+        const double kj = gj < n ? k[gj] : 0.0;
+        double tv = tom_value(stage_t[jl * kNbOutLd + lane], a, ki, kj);
+        tv = gi == gj ? 1.0 : tv;
+        if (in && (!diag || gi >= gj)) bad |= isfinite(tv) ? 0 : 4;
+        stage_t[jl * kNbOutLd + lane] = tv;
+      }
+      __syncthreads();
+      // (i, j): one column of 64 rows per wave instruction
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int jl = 8 * wave + q;
+        const int64_t gj = J * kNbTile + 32 * h + jl;
+        if (gi < n && gj < n && (!diag || gi >= gj)) net[2 * (gi + gj * n)] = stage_t[jl * kNbOutLd + lane];
+      }
+      // (j, i): two rows i of 32 columns j per wave instruction
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const int il = 16 * wave + 2 * q + (lane >> 5), jl = lane & 31;
+        const int64_t mi = I * kNbTile + il, mj = J * kNbTile + 32 * h + jl;
+        if (mi < n && mj < n && (!diag || mi >= mj)) net[2 * (mj + mi * n)] = stage_t[jl * kNbOutLd + il];
+      }
+      __syncthreads();
+    }
+  }
+  // one reduction per wave, one atomic per wave that saw a non-finite value
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad |= __shfl_xor(bad, o, 64);
+  if (bad && lane == 0) atomicOr(flags, bad);
+}
+
 // corr[e] / net[e] of elements [first, first + len) of a pair array with
 // element stride es (1: {corr, net}; 2: the Gram-table layout).
 __global__ void deinterleave_kernel(const double2* __restrict__ pairs, int es, int64_t first, int64_t len,
@@ -266,6 +407,24 @@ hipError_t launch_netbuild(const double* X, int64_t S, int64_t n, double2* pairs
   const int64_t n_tiles = nT * (nT + 1) / 2;
   const unsigned g = (unsigned)std::min<int64_t>(n_tiles, (int64_t)1 << 20);
   hipLaunchKernelGGL(netbuild_kernel, dim3(g), dim3(256), 0, st, X, S, n, pairs, net_type, beta, flags);
+  return hipGetLastError();
+}
+
+size_t tom_scratch_bytes(int64_t n) {
+  return ((size_t)n * (size_t)(n + 2) + (size_t)n) * sizeof(double);
+}
+
+hipError_t launch_tom(int64_t n, double2* pairs, double* scratch, int* flags, hipStream_t st) {
+  double* const A = scratch;
+  double* const k = scratch + n * (n + 2);
+  const unsigned ge = (unsigned)std::min<int64_t>(n + 2, (int64_t)1 << 20);
+  hipLaunchKernelGGL(tom_extract_kernel, dim3(ge), dim3(256), 0, st, pairs, n, A, k);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  const int64_t nT = (n + kNbTile - 1) / kNbTile;
+  const int64_t n_tiles = nT * (nT + 1) / 2;
+  const unsigned g = (unsigned)std::min<int64_t>(n_tiles, (int64_t)1 << 20);
+  hipLaunchKernelGGL(tom_kernel, dim3(g), dim3(256), 0, st, A, k, n, pairs, flags);
   return hipGetLastError();
 }
 

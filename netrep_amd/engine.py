@@ -90,19 +90,22 @@ class Engine:
         self.n_nodes = n
         self.n_samples = s
 
-    def set_dataset_from_data(self, data, beta, net_type="unsigned", scale=True):
+    def set_dataset_from_data(self, data, beta, net_type="unsigned", scale=True, tom=False):
         """The resident dataset from the data matrix alone (S x N, host numpy):
         only `data` is uploaded (scaled on the device unless ``scale=False``:
         already scaled); corr = cor(data) and net (``net_type`` 'unsigned'
         |corr|^beta, 'signed' ((1 + corr) / 2)^beta, 'signed_hybrid' corr^beta
-        for corr > 0, else 0) are built in HBM (nr_set_dataset_from_data)."""
+        for corr > 0, else 0) are built in HBM (nr_set_dataset_from_data).
+        ``tom=True``: the resident net is the topological overlap matrix of
+        that adjacency (NR_NET_TOM: WGCNA's unsigned TOM, TOMDenom "min"),
+        computed on the device too; corr is the same either way."""
         d = _f64(data)
         if d.ndim != 2:
             raise ValueError("data must be a samples x nodes matrix")
         s, n = d.shape
         self._check(self._lib.nr_set_dataset_from_data(self._h, _ptr(d), n, s, L.NR_HOST,
                                                        L.NR_SCALE_DATA if scale else 0,
-                                                       L.net_type_code(net_type), float(beta)))
+                                                       L.net_type_code(net_type, tom), float(beta)))
         self.n_stat = 7
         self.n_nodes = n
         self.n_samples = s
@@ -121,6 +124,15 @@ class Engine:
         the figure of the dataset it was copied from."""
         ms = C.c_double()
         self._check(self._lib.nr_netbuild_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def tom_ms(self) -> float:
+        """Device time in ms of the topological-overlap step of a from-data
+        build with ``tom=True`` (nr_tom_ms: extract, degrees and the TOM
+        kernel; not part of netbuild_ms), 0 for any other dataset. A copy
+        reports its source's figure."""
+        ms = C.c_double()
+        self._check(self._lib.nr_tom_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
     def set_dataset_files(self, corr_path, net_path, data_path=None, objects=(None, None, None),
