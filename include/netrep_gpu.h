@@ -107,6 +107,43 @@ int nr_set_dataset_ex(nr_ctx* ctx, const double* corr, const double* net,
  * NR_ERR_OOM and leaves no dataset resident. Any other net_type value stays
  * NR_ERR_INVALID. */
 #define NR_NET_TOM 0x10
+/* The correlation type, OR-ed onto net_type as NR_NET_TOM is (neither bit:
+ * Pearson, exactly as above). net_type is (0|1|2) | (0|0x10) | (0|0x100|0x200);
+ * both correlation bits together return NR_ERR_INVALID "unknown correlation
+ * type", every other value NR_ERR_INVALID "unknown network type", before
+ * anything touches the GPU. With X the resident data block (S x n, scaled as
+ * by Scale whether or not NR_SCALE_DATA was given), a correlation type makes
+ * a second, transient S x n matrix Z from X, column by column, and
+ *   corr(i,j) = clamp(z_i . z_j / (S - 1), -1, 1)
+ * by the same kernel, run on Z instead of X; the clamp, the network types,
+ * NR_NET_TOM, the mirrored stores and the finite flags are as above. X stays
+ * the dataset's data block: the Gram table and all seven statistics run on it
+ * unchanged.
+ *   NR_COR_SPEARMAN: z = Scale(r) with r_i = L_i + (E_i + 1) / 2, L_i the
+ *     number of entries of the column less than x_i, E_i the number equal to
+ *     it (itself included): R's rank(ties.method = "average"), exact. +-Inf
+ *     are ranked like any value, as R does; a column holding a NaN becomes
+ *     all NaN; a constant column has sd 0 and becomes NaN, as for Pearson.
+ *   NR_COR_BICOR: WGCNA's bicor with its defaults (maxPOutliers = 1,
+ *     pearsonFallback = "individual"). med = median of the column, always
+ *     0.5 (lo + hi) of the order statistics at 0-based positions (S - 1) / 2
+ *     and S / 2; d_i = |x_i - med|; mad = median of d (no 1.4826 factor);
+ *     u_i = (x_i - med) / (9 mad); w_i = (1 - u_i^2)^2 where |u_i| < 1, else
+ *     0; a_i = (x_i - med) w_i; if mad == 0, a_i = x_i - mean(x) (the Pearson
+ *     fallback for that column alone); z_i = a_i sqrt(S - 1) / sqrt(sum a^2).
+ *     A column with any non-finite entry becomes all NaN; an all-zero a (a
+ *     constant column) gives 0 / 0 = NaN.
+ * Both read the *scaled* block. Both are invariant under a column's positive
+ * affine map, so scaling changes nothing except where its rounding merges two
+ * distinct raw values into a tie. Ranks and order statistics come from exact
+ * counting (no atomics, independent of scheduling); the sums run in a fixed
+ * order. Device scratch for the call: 8 S (n + 2) bytes for Z and, for
+ * Spearman, 8 S n for the ranks; freed before the call returns; when the
+ * allocation fails the call returns NR_ERR_OOM and leaves no dataset
+ * resident. Order of work on the context's stream: transform (+ scale), the
+ * build on Z, the optional TOM. */
+#define NR_COR_SPEARMAN 0x100
+#define NR_COR_BICOR 0x200
 int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples,
                              int where, int flags, int net_type, double beta);
 /* Device time in ms (HIP events on the context's stream) of the kernel that
@@ -119,6 +156,11 @@ int nr_netbuild_ms(nr_ctx* ctx, double* ms);
  * 0 for a dataset built without NR_NET_TOM or made any other way. A copy
  * reports its source's figure. */
 int nr_tom_ms(nr_ctx* ctx, double* ms);
+/* Device time in ms of the correlation-type transform ahead of that kernel
+ * (NR_COR_SPEARMAN: ranks and their scaling; NR_COR_BICOR: the bicor
+ * columns; neither nr_netbuild_ms nor nr_tom_ms includes it); 0 for Pearson
+ * or a dataset made any other way. A copy reports its source's figure. */
+int nr_cor_ms(nr_ctx* ctx, double* ms);
 /* The resident corr and net (n_nodes x n_nodes each, column-major) to host
  * arrays; either may be NULL. Works for a dataset made by any of the
  * set-dataset calls, before or after the Gram table is built: the pairs are
@@ -460,7 +502,8 @@ int netrep_PermutationProcedureFiles(const netrep_disc_props* disc_props, const 
  * (nr_set_dataset_from_data on GPU 0: t_data is uploaded, scaled there when
  * scale_data != 0, and the correlation and network are built in HBM from it
  * by net_type (NR_NET_*, with NR_NET_TOM OR-ed on: the network is the
- * topological overlap of that adjacency) and beta; no n x n host matrix exists or crosses
+ * topological overlap of that adjacency; with NR_COR_SPEARMAN or NR_COR_BICOR
+ * OR-ed on: the correlation is of that type) and beta; no n x n host matrix exists or crosses
  * PCIe). Built matrices that are not all finite -- a constant column, for
  * which R's cor gives NA -- return NR_ERR_NONFINITE with CheckFinite's
  * message before any permutation runs (the reference stops such input in

@@ -30,9 +30,13 @@ NR_NET_UNSIGNED = 0
 NR_NET_SIGNED = 1
 NR_NET_SIGNED_HYBRID = 2
 NR_NET_TOM = 0x10   # OR-ed onto one of the three: the network is the TOM of that adjacency
+NR_COR_SPEARMAN = 0x100   # OR-ed on likewise: the correlation type (neither: Pearson)
+NR_COR_BICOR = 0x200
 # networkType names of the from-data entries (WGCNA's spelling accepted too)
 NET_TYPES = {"unsigned": NR_NET_UNSIGNED, "signed": NR_NET_SIGNED, "signed_hybrid": NR_NET_SIGNED_HYBRID,
              "signed hybrid": NR_NET_SIGNED_HYBRID}
+# corType names of the from-data entries
+COR_TYPES = {"pearson": 0, "spearman": NR_COR_SPEARMAN, "bicor": NR_COR_BICOR}
 
 
 class NetRepError(RuntimeError):
@@ -139,6 +143,7 @@ SIGNATURES = {
     "nr_set_dataset_from_data": (_int, [_p, _dp, _i64, _i64, _int, _int, _int, C.c_double]),
     "nr_netbuild_ms": (_int, [_p, C.POINTER(C.c_double)]),
     "nr_tom_ms": (_int, [_p, C.POINTER(C.c_double)]),
+    "nr_cor_ms": (_int, [_p, C.POINTER(C.c_double)]),
     "nr_get_dataset_matrices": (_int, [_p, _dp, _dp]),
     "netrep_PermutationProcedureFromData": (_int, [C.POINTER(DiscProps), _dp, _i32, _i32, C.c_double, _i64, _i64,
                                                    _strv, _strv, _strv, _i64, _strv, _i64, _i64, _i32, C.c_char_p,
@@ -188,13 +193,18 @@ def load() -> C.CDLL:
     return lib
 
 
-def net_type_code(network_type, tom=False) -> int:
-    """NR_NET_* of a networkType name; with ``tom``, NR_NET_TOM OR-ed on."""
+def net_type_code(network_type, tom=False, cor_type="pearson") -> int:
+    """NR_NET_* of a networkType name; with ``tom``, NR_NET_TOM OR-ed on; with
+    ``cor_type`` 'spearman' or 'bicor', NR_COR_SPEARMAN / NR_COR_BICOR."""
     key = str(network_type).lower().replace("-", "_")
     if key not in NET_TYPES:
         raise NetRepError(NR_ERR_INVALID, f"unknown networkType {network_type!r}: one of "
                                           "'unsigned', 'signed', 'signed_hybrid'")
-    return NET_TYPES[key] | (NR_NET_TOM if tom else 0)
+    cor = str(cor_type).lower()
+    if cor not in COR_TYPES:
+        raise NetRepError(NR_ERR_INVALID, f"unknown corType {cor_type!r}: one of "
+                                          "'pearson', 'spearman', 'bicor'")
+    return NET_TYPES[key] | (NR_NET_TOM if tom else 0) | COR_TYPES[cor]
 
 
 def check(rc: int, ctx=None) -> None:

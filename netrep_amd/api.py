@@ -445,7 +445,7 @@ def PermutationProcedureFromData(discProps: dict, tData: RMatrix, beta: float, m
                                  nPermutations: int, nCores: int = 1, nullHypothesis: str = "overlap",
                                  verbose: bool = False, seed: int = DEFAULT_SEED, pi=None,
                                  networkType: str = "unsigned", scaleData: bool = False,
-                                 tom: bool = False) -> dict:
+                                 tom: bool = False, corType: str = "pearson") -> dict:
     """PermutationProcedure on a test dataset given as its data matrix alone
     (netrep_PermutationProcedureFromData): ``tData`` (samples x nodes, its
     colnames the node names; scaled already unless ``scaleData``) is the only
@@ -453,7 +453,10 @@ def PermutationProcedureFromData(discProps: dict, tData: RMatrix, beta: float, m
     'unsigned' |cor|^beta, 'signed' ((1 + cor) / 2)^beta, 'signed_hybrid'
     cor^beta where cor > 0, else 0; with ``tom=True`` the topological overlap
     matrix of that adjacency, WGCNA's unsigned TOM with TOMDenom "min") are
-    built on the GPU. Raises
+    built on the GPU. ``corType`` 'spearman' or 'bicor' (WGCNA's bicor with
+    its defaults): the correlation is of that type, computed on the GPU from
+    the resident scaled data, which stay what the data statistics (coherence,
+    cor.contrib, avg.contrib) are computed from. Raises
     ``NetRepError`` (``NR_ERR_NONFINITE``) if they are not all finite, e.g.
     for a constant column."""
     lib = L.load()
@@ -484,7 +487,7 @@ def PermutationProcedureFromData(discProps: dict, tData: RMatrix, beta: float, m
     if verbose and not _progress_user_set:
         _install_progress(_print_progress)
     rc = lib.netrep_PermutationProcedureFromData(
-        C.byref(dp), _dptr(data), int(bool(scaleData)), L.net_type_code(networkType, tom), float(beta), s, n, tn,
+        C.byref(dp), _dptr(data), int(bool(scaleData)), L.net_type_code(networkType, tom, corType), float(beta), s, n, tn,
         an,
         al, len(names), mo, nm_, int(nPermutations), int(nCores), str(nullHypothesis).encode(),
         int(bool(verbose)), int(seed) & (2**64 - 1),
@@ -493,19 +496,23 @@ def PermutationProcedureFromData(discProps: dict, tData: RMatrix, beta: float, m
     return _permutation_result(rc, modules, True, observed, nulls, nPermutations)
 
 
-def BuildNetwork(data, beta: float, networkType: str = "unsigned", scaleData: bool = True, tom: bool = False):
+def BuildNetwork(data, beta: float, networkType: str = "unsigned", scaleData: bool = True, tom: bool = False,
+                 corType: str = "pearson"):
     """(correlation, network) of a data matrix, built on the GPU as the from-data
     path builds them (netrep_BuildNetwork) and copied back, for callers who
     still need host matrices (the discovery-side calls). ``data`` is raw
     unless ``scaleData=False``. ``tom=True``: the network returned is the
-    topological overlap matrix of the adjacency. Node names: the data's
+    topological overlap matrix of the adjacency. ``corType`` 'spearman' or
+    'bicor': the correlation returned is Spearman's or WGCNA's biweight
+    midcorrelation (and the network is built from it). Node names: the data's
     colnames."""
     m = data if isinstance(data, RMatrix) else RMatrix(np.asarray(data))
     x = m.f
     s, n = x.shape
     corr = np.empty((n, n), order="F")
     net = np.empty((n, n), order="F")
-    L.check_api(L.load().netrep_BuildNetwork(_dptr(x), int(bool(scaleData)), L.net_type_code(networkType, tom),
+    L.check_api(L.load().netrep_BuildNetwork(_dptr(x), int(bool(scaleData)),
+                                             L.net_type_code(networkType, tom, corType),
                                              float(beta), s, n, _dptr(corr), _dptr(net)))
     return RMatrix(corr, m.colnames, m.colnames), RMatrix(net, m.colnames, m.colnames)
 

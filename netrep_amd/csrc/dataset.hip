@@ -337,10 +337,12 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
   if (!data) return fail(ctx, NR_ERR_INVALID, "data missing");
   if (n_nodes < 1 || n_samples < 2) return fail(ctx, NR_ERR_INVALID, "data needs n_nodes >= 1 and n_samples >= 2");
   if (where != NR_HOST && where != NR_DEVICE) return fail(ctx, NR_ERR_INVALID, "where must be NR_HOST or NR_DEVICE");
-  const int base_type = net_type & ~NR_NET_TOM;
+  const int cor_type = net_type & (NR_COR_SPEARMAN | NR_COR_BICOR);
+  const int base_type = net_type & ~(NR_NET_TOM | NR_COR_SPEARMAN | NR_COR_BICOR);
   const bool tom = (net_type & NR_NET_TOM) != 0;
   if (base_type != NR_NET_UNSIGNED && base_type != NR_NET_SIGNED && base_type != NR_NET_SIGNED_HYBRID)
     return fail(ctx, NR_ERR_INVALID, "unknown network type");
+  if (cor_type == (NR_COR_SPEARMAN | NR_COR_BICOR)) return fail(ctx, NR_ERR_INVALID, "unknown correlation type");
   if (!std::isfinite(beta) || beta <= 0.0) return fail(ctx, NR_ERR_INVALID, "beta must be finite and > 0");
   if (n_nodes > (int64_t)INT32_MAX) return fail(ctx, NR_ERR_UNSUPPORTED, "n_nodes exceeds 2^31-1");
   return replace_dataset(ctx, [&](Dataset& ds) -> int {
@@ -366,7 +368,21 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
       ~Scratch() {
         if (p) (void)hipFree(p);
       }
-    } tom_scratch;
+    } tom_scratch, cor_scratch;
+    // The correlation-type scratch (kernels.h, launch_cor_transform): Z in the
+    // data block's shape, S x (n + 2) with both padding columns zero, and for
+    // Spearman the plain S x n rank buffer behind it; for this call only.
+    if (cor_type) {
+      const size_t cor_bytes = nr::cor_scratch_bytes(n_nodes, n_samples, cor_type);
+      if (hipMalloc((void**)&cor_scratch.p, cor_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        cor_scratch.p = nullptr;
+        return fail(ctx, NR_ERR_OOM,
+                    "from-data dataset: allocation of the " + std::to_string(cor_bytes) + "-byte (" +
+                        std::to_string(cor_bytes >> 20) + " MiB) correlation-type scratch failed (8 S (n + 2)" +
+                        (cor_type == NR_COR_SPEARMAN ? " + 8 S n" : "") + " bytes)");
+      }
+    }
     if (tom) {
       const size_t tom_bytes = nr::tom_scratch_bytes(n_nodes);
       if (hipMalloc((void**)&tom_scratch.p, tom_bytes) != hipSuccess) {
@@ -378,16 +394,26 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
       }
     }
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t ev_cor = nullptr;  // the start of the transform step, which ends at ev[0]
     hipError_t e = hipSuccess;
     for (hipEvent_t& x : ev)
       if (e == hipSuccess) e = hipEventCreate(&x);
-    float ms = 0.f, ms_tom = 0.f;
+    if (e == hipSuccess && cor_type) e = hipEventCreate(&ev_cor);
+    float ms = 0.f, ms_tom = 0.f, ms_cor = 0.f;
+    // what netbuild_kernel runs on: the data block, or the transform's Z
+    const double* const build_from = cor_type ? cor_scratch.p : ds.d_data;
     // one flag word for both epilogues: netbuild's, then the TOM's on top
     if (e == hipSuccess)
       rc = read_flags(ctx, ds, "from-data build", [&](int* flag) {
-        hipError_t p = hipEventRecord(ev[0], ctx->stream);
+        hipError_t p = hipSuccess;
+        if (cor_type) {
+          p = hipEventRecord(ev_cor, ctx->stream);
+          if (p == hipSuccess)
+            p = nr::launch_cor_transform(ds.d_data, n_samples, n_nodes, cor_type, cor_scratch.p, ctx->stream);
+        }
+        if (p == hipSuccess) p = hipEventRecord(ev[0], ctx->stream);
         if (p == hipSuccess)
-          p = nr::launch_netbuild(ds.d_data, n_samples, n_nodes, ds.d_pairs, base_type, beta, flag, ctx->stream);
+          p = nr::launch_netbuild(build_from, n_samples, n_nodes, ds.d_pairs, base_type, beta, flag, ctx->stream);
         if (p == hipSuccess) p = hipEventRecord(ev[1], ctx->stream);
         if (p == hipSuccess && tom) p = nr::launch_tom(n_nodes, ds.d_pairs, tom_scratch.p, flag, ctx->stream);
         if (p == hipSuccess) p = hipEventRecord(ev[2], ctx->stream);
@@ -395,12 +421,15 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
       });
     if (e == hipSuccess && !rc) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
     if (e == hipSuccess && !rc && tom) e = hipEventElapsedTime(&ms_tom, ev[1], ev[2]);
+    if (e == hipSuccess && !rc && cor_type) e = hipEventElapsedTime(&ms_cor, ev_cor, ev[0]);
     for (hipEvent_t x : ev)
       if (x) (void)hipEventDestroy(x);
+    if (ev_cor) (void)hipEventDestroy(ev_cor);
     if (rc) return rc;
     if (e != hipSuccess) return hip_fail(ctx, e, "from-data build");
     ds.netbuild_ms = (double)ms;
     ds.tom_ms = (double)ms_tom;
+    ds.cor_ms = (double)ms_cor;
     ds.symmetric = 1;  // every tile is stored and mirrored from the same bits
     ds.n_nodes = n_nodes;
     ds.n_samples = n_samples;
@@ -673,6 +702,12 @@ int nr_netbuild_ms(nr_ctx* ctx, double* ms) {
 int nr_tom_ms(nr_ctx* ctx, double* ms) {
   if (!ctx || !ms) return NR_ERR_INVALID;
   *ms = ctx->ds.d_pairs ? ctx->ds.tom_ms : 0.0;
+  return NR_OK;
+}
+
+int nr_cor_ms(nr_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return NR_ERR_INVALID;
+  *ms = ctx->ds.d_pairs ? ctx->ds.cor_ms : 0.0;
   return NR_OK;
 }
 

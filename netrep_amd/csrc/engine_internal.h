@@ -33,6 +33,7 @@ struct Dataset {
   double table_ms = 0.0;         // wall time of the last Gram-table build
   double netbuild_ms = 0.0;      // device time of the from-data build of the matrices (0: not built from data)
   double tom_ms = 0.0;           // device time of the TOM step behind it (0: built without NR_NET_TOM)
+  double cor_ms = 0.0;           // device time of the correlation-type transform ahead of it (0: Pearson)
 };
 
 struct nr_ctx {

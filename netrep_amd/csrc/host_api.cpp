@@ -746,9 +746,12 @@ namespace {
 int check_from_data_args(const double* data, int32_t net_type, double beta, int64_t n_samples, int64_t n_nodes) {
   if (!data) return set_err(NR_ERR_INVALID, "data missing");
   if (n_samples < 2 || n_nodes < 1) return set_err(NR_ERR_INVALID, "data needs n_samples >= 2 and n_nodes >= 1");
-  const int32_t base_type = net_type & ~NR_NET_TOM;  // NR_NET_TOM may ride on any of the three
+  // NR_NET_TOM and one correlation type may ride on any of the three
+  const int32_t cor_type = net_type & (NR_COR_SPEARMAN | NR_COR_BICOR);
+  const int32_t base_type = net_type & ~(NR_NET_TOM | NR_COR_SPEARMAN | NR_COR_BICOR);
   if (base_type != NR_NET_UNSIGNED && base_type != NR_NET_SIGNED && base_type != NR_NET_SIGNED_HYBRID)
     return set_err(NR_ERR_INVALID, "unknown network type");
+  if (cor_type == (NR_COR_SPEARMAN | NR_COR_BICOR)) return set_err(NR_ERR_INVALID, "unknown correlation type");
   if (!std::isfinite(beta) || beta <= 0.0) return set_err(NR_ERR_INVALID, "beta must be finite and > 0");
   return NR_OK;
 }

@@ -193,6 +193,20 @@ hipError_t launch_netbuild(const double* X, int64_t S, int64_t n, double2* pairs
 // flags |= 4 for a non-finite t.
 size_t tom_scratch_bytes(int64_t n);
 hipError_t launch_tom(int64_t n, double2* pairs, double* scratch, int* flags, hipStream_t st);
+// The correlation types other than Pearson (cortransform.hip; NR_COR_SPEARMAN,
+// NR_COR_BICOR): Z, S x (n + 2) with both padding columns zero, from the scaled
+// block X, for launch_netbuild to run on instead of X. scratch:
+// cor_scratch_bytes(n, S, cor_type) bytes (0 for Pearson): Z and, for
+// Spearman, the plain S x n rank buffer behind it that launch_scale turns into
+// Z. A column is staged in LDS up to kCorLdsRows rows (beyond: swept in global
+// memory); up to kCorWaveRows rows a wave owns a column and a workgroup holds
+// four (cor_cols_per_workgroup), above that a workgroup owns one.
+constexpr int kCorLdsRows = 2048;
+constexpr int kCorWaveRows = kCorLdsRows / 4;
+int cor_cols_per_workgroup(int64_t S);
+size_t cor_scratch_bytes(int64_t n, int64_t S, int cor_type);
+hipError_t launch_cor_transform(const double* X, int64_t S, int64_t n, int cor_type, double* scratch,
+                                hipStream_t st);
 // corr[e], net[e] (either may be NULL) = elements [first, first + len) of a
 // pair array in layout es (1, or 2: the Gram table).
 hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,

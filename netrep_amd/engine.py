@@ -36,6 +36,11 @@ class Engine:
 
     # side of the from-data kernel's workgroup tile (kNetbuildTile, csrc/kernels.h)
     NETBUILD_TILE = 64
+    # rows of a column the correlation-type kernels stage in LDS (kCorLdsRows,
+    # csrc/kernels.h): longer columns are swept in global memory. Up to a
+    # quarter of it (COR_WAVE_ROWS) a wave owns a column, four per workgroup.
+    COR_LDS_ROWS = 2048
+    COR_WAVE_ROWS = COR_LDS_ROWS // 4
 
     def __init__(self, device: int = 0):
         self._lib = L.load()
@@ -90,7 +95,7 @@ class Engine:
         self.n_nodes = n
         self.n_samples = s
 
-    def set_dataset_from_data(self, data, beta, net_type="unsigned", scale=True, tom=False):
+    def set_dataset_from_data(self, data, beta, net_type="unsigned", scale=True, tom=False, cor_type="pearson"):
         """The resident dataset from the data matrix alone (S x N, host numpy):
         only `data` is uploaded (scaled on the device unless ``scale=False``:
         already scaled); corr = cor(data) and net (``net_type`` 'unsigned'
@@ -98,14 +103,19 @@ class Engine:
         for corr > 0, else 0) are built in HBM (nr_set_dataset_from_data).
         ``tom=True``: the resident net is the topological overlap matrix of
         that adjacency (NR_NET_TOM: WGCNA's unsigned TOM, TOMDenom "min"),
-        computed on the device too; corr is the same either way."""
+        computed on the device too; corr is the same either way.
+        ``cor_type`` 'spearman' (the correlation of the average ranks) or
+        'bicor' (WGCNA's biweight midcorrelation with its defaults): corr is
+        of that type, from a transient transform of the resident scaled
+        block; the data block itself, and so the data statistics, stay the
+        scaled data (include/netrep_gpu.h has the definitions)."""
         d = _f64(data)
         if d.ndim != 2:
             raise ValueError("data must be a samples x nodes matrix")
         s, n = d.shape
         self._check(self._lib.nr_set_dataset_from_data(self._h, _ptr(d), n, s, L.NR_HOST,
                                                        L.NR_SCALE_DATA if scale else 0,
-                                                       L.net_type_code(net_type, tom), float(beta)))
+                                                       L.net_type_code(net_type, tom, cor_type), float(beta)))
         self.n_stat = 7
         self.n_nodes = n
         self.n_samples = s
@@ -133,6 +143,15 @@ class Engine:
         reports its source's figure."""
         ms = C.c_double()
         self._check(self._lib.nr_tom_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def cor_ms(self) -> float:
+        """Device time in ms of the correlation-type transform of a from-data
+        build with ``cor_type`` 'spearman' or 'bicor' (nr_cor_ms; not part of
+        netbuild_ms or tom_ms), 0 for Pearson or any other dataset. A copy
+        reports its source's figure."""
+        ms = C.c_double()
+        self._check(self._lib.nr_cor_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
     def set_dataset_files(self, corr_path, net_path, data_path=None, objects=(None, None, None),
