@@ -161,6 +161,55 @@ int nr_tom_ms(nr_ctx* ctx, double* ms);
  * columns; neither nr_netbuild_ms nor nr_tom_ms includes it); 0 for Pearson
  * or a dataset made any other way. A copy reports its source's figure. */
 int nr_cor_ms(nr_ctx* ctx, double* ms);
+
+/* The soft-threshold connectivities of WGCNA's pickSoftThreshold, from the
+ * data matrix alone: for each of the n_powers candidate powers,
+ *   k_out[i + m n_nodes] = sum over u != i of b_iu ^ powers[m]
+ * with c = clamp(x_i . x_u / (n_samples - 1), -1, 1) of the scaled data (or,
+ * with NR_COR_SPEARMAN / NR_COR_BICOR in net_type, of its transform Z as
+ * nr_set_dataset_from_data makes it), written as that call's kernel writes
+ * it so that NaN stays NaN, and the base b of net_type:
+ *   |c|                  NR_NET_UNSIGNED
+ *   (1 + c) / 2          NR_NET_SIGNED
+ *   c > 0 ? c : 0        NR_NET_SIGNED_HYBRID (NaN propagates)
+ * The diagonal is left out (WGCNA sums it and subtracts 1); n_nodes = 1
+ * gives k = 0; a column that is NaN (a constant column) makes every k NaN.
+ * powers: finite and > 0, their order and duplicates kept (duplicates come
+ * out bitwise equal), n_powers <= 32. If every power is an integer <= 64,
+ * b^p comes from one multiplication chain b, b b, (b b) b, ... per element;
+ * otherwise every power takes one pow(b, p). `data` is host memory,
+ * n_samples x n_nodes, raw (scale != 0: scaled on the device) or scaled as by
+ * Scale (scale == 0). NR_ERR_INVALID before anything touches the GPU: a NULL
+ * pointer, n_samples < 2, n_nodes < 1, n_powers outside 1 .. 32, a power not
+ * finite or <= 0, NR_NET_TOM in net_type ("NR_NET_TOM has no soft-threshold
+ * connectivity"), any other unknown type.
+ * No n x n array exists at any time. Only `data` is uploaded, into a
+ * transient block; one workgroup per (64-column tile, row group) runs the
+ * from-data kernel's SYRK main loop over its row tiles of the full matrix
+ * and keeps one running sum per distinct power and column in registers; a
+ * second kernel adds the R row groups in increasing order. No floating-point
+ * atomics: the result is bitwise repeatable and a function of the inputs and
+ * R alone; R is a function of n_nodes alone (ceil(ceil(n / 64) / 16), at most
+ * 32), never of the device. Device memory for the call, all freed before it
+ * returns on every path: the block, 8 S (n + 2) bytes (8 S n more while it is
+ * scaled), the correlation-type scratch, and 8 R P n + 8 P n bytes of partial
+ * sums and result; a failed allocation returns NR_ERR_OOM naming the bytes.
+ * The context's resident dataset, modules, null pool and per-batch buffers
+ * are not touched. */
+int nr_soft_connectivity(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples, int scale,
+                         int net_type, const double* powers, int n_powers, double* k_out);
+/* Device time in ms (HIP events) of the two kernels of the context's last
+ * nr_soft_connectivity call (not the upload, scaling or transform); 0 before
+ * the first. */
+int nr_sft_ms(nr_ctx* ctx, double* ms);
+/* 1 if every connectivity of that call was finite (the reduction kernel's
+ * flag word, as nr_dataset_finite reports the build's), else 0. */
+int nr_sft_finite(nr_ctx* ctx, int* finite);
+/* Test knob: the number of row groups R of later nr_soft_connectivity calls
+ * on this context (1 .. 1024; more groups than row tiles leaves the surplus
+ * empty); 0 restores the default. It regroups the sums, so k moves at
+ * rounding level. */
+int nr_set_sft_row_groups(nr_ctx* ctx, int row_groups);
 /* The resident corr and net (n_nodes x n_nodes each, column-major) to host
  * arrays; either may be NULL. Works for a dataset made by any of the
  * set-dataset calls, before or after the Gram table is built: the pairs are
@@ -524,6 +573,44 @@ int netrep_PermutationProcedureFromData(
  * topological overlap matrix. Non-finite results are returned as they are. */
 int netrep_BuildNetwork(const double* data, int32_t scale_data, int32_t net_type, double beta,
                         int64_t n_samples, int64_t n_nodes, double* corr_out, double* net_out);
+
+/* WGCNA's scaleFreeFitIndex of one connectivity vector k[n], with R's
+ * current cut() binning; a pure host function (no context, no GPU).
+ * B = n_breaks >= 3 bins over [min k, max k]: dx = max k - min k, edges
+ * e_m = min k + m (dx / B), m = 0 .. B; node i is in bin 1 + #{m in
+ * 1 .. B - 1 : k_i > e_m} (right-closed bins; the minimum is in bin 1, the
+ * maximum in bin B). Per bin: p_m = count_m / n; d_m = the mean of k in the
+ * bin, or (e_{m-1} + e_m) / 2 if the bin is empty or that mean is 0;
+ * x_m = log10(d_m), y_m = log10(p_m + 1e-9). remove_first drops bin 1; N
+ * bins remain. out3[0] = R^2 = 1 - SSR / SST of the least-squares line
+ * y ~ x (SFT.R.sq), out3[1] = its slope, out3[2] = the adjusted R^2
+ * 1 - (1 - R^2) (N - 1) / (N - 3) of the least-squares fit y ~ x + d
+ * (truncated.R.sq; NaN for N <= 3). dx == 0 or a non-finite k: three NaNs.
+ * NR_ERR_INVALID: a NULL pointer, n < 1, n_breaks < 3. */
+int netrep_ScaleFreeFit(const double* k, int64_t n, int32_t n_breaks, int32_t remove_first, double* out3);
+/* The bin (1 .. n_breaks) of every node under that binning into
+ * bins_out[n]; all 0 where netrep_ScaleFreeFit gives NaNs. */
+int netrep_ScaleFreeBins(const double* k, int64_t n, int32_t n_breaks, int32_t* bins_out);
+/* powerEstimate of a pickSoftThreshold table (n_powers x 7, column-major:
+ * Power, SFT.R.sq, slope, ...): the first power, in the table's order, with
+ * -sign(slope) SFT.R.sq > rsquared_cut; NaN if none passes (a NaN row does
+ * not). A pure host function. */
+int netrep_SftPowerEstimate(const double* table, int32_t n_powers, double rsquared_cut, double* power_estimate_out);
+/* WGCNA's pickSoftThreshold from the data matrix alone: the connectivities
+ * of nr_soft_connectivity on GPU 0 (data raw when scale_data != 0, else
+ * scaled already; net_type as there), then per power the fit above and
+ * the table row Power, SFT.R.sq, slope, truncated.R.sq, mean.k., median.k.
+ * (R's: the mean of the two middle values for even n), max.k. into
+ * table_out (n_powers x 7, column-major); *power_estimate_out as
+ * netrep_SftPowerEstimate; connectivity_out (optional, n_nodes x n_powers,
+ * column-major) receives the connectivities. Connectivities that are not all
+ * finite -- a constant column -- return NR_ERR_NONFINITE as the other
+ * from-data entries do. Every argument check (those of nr_soft_connectivity,
+ * n_breaks >= 3, rsquared_cut not NaN) runs before a context is opened. */
+int netrep_PickSoftThreshold(const double* data, int32_t scale_data, int32_t net_type, int64_t n_samples,
+                             int64_t n_nodes, const double* powers, int32_t n_powers, double rsquared_cut,
+                             int32_t n_breaks, int32_t remove_first, double* table_out,
+                             double* power_estimate_out, double* connectivity_out);
 
 /* Host read of one numeric matrix from an RDS file or save() archive (the
  * same reader): dims always; values (column-major, native) into `out` when

@@ -11,7 +11,7 @@ from ._lib import NetRepError, load  # noqa: F401
 from .api import (CheckFinite, IntermediateProperties, IntermediatePropertiesNoData,  # noqa: F401
                   NetProps, NetPropsNoData, PermutationProcedure, PermutationProcedureNoData,
                   PrefetchTestDataset, DiscardPrefetch, ReleaseResident, h2d_bytes, PermutationProcedureFiles, RMatrix,
-                  PermutationProcedureFromData, BuildNetwork,
+                  PermutationProcedureFromData, BuildNetwork, PickSoftThreshold, ScaleFreeFit,
                   read_rds_matrix, Scale, STATNAMES, STATNAMES_NODATA,
                   set_interrupt_hook)
 from .engine import Engine, device_count, prp_table  # noqa: F401
@@ -21,4 +21,4 @@ __all__ = ["CheckFinite", "IntermediateProperties", "IntermediatePropertiesNoDat
            "Scale", "Engine", "NetRepError", "device_count", "prp_table", "STATNAMES",
            "STATNAMES_NODATA", "set_interrupt_hook", "PrefetchTestDataset",
            "DiscardPrefetch", "ReleaseResident", "h2d_bytes", "PermutationProcedureFiles", "read_rds_matrix",
-           "PermutationProcedureFromData", "BuildNetwork"]
+           "PermutationProcedureFromData", "BuildNetwork", "PickSoftThreshold", "ScaleFreeFit"]

@@ -149,6 +149,15 @@ SIGNATURES = {
                                                    _strv, _strv, _strv, _i64, _strv, _i64, _i64, _i32, C.c_char_p,
                                                    _i32, _u64, _u32p, _dp, _dp]),
     "netrep_BuildNetwork": (_int, [_dp, _i32, _i32, C.c_double, _i64, _i64, _dp, _dp]),
+    "nr_soft_connectivity": (_int, [_p, _dp, _i64, _i64, _int, _int, _dp, _int, _dp]),
+    "nr_sft_ms": (_int, [_p, C.POINTER(C.c_double)]),
+    "nr_sft_finite": (_int, [_p, _intp]),
+    "nr_set_sft_row_groups": (_int, [_p, _int]),
+    "netrep_ScaleFreeFit": (_int, [_dp, _i64, _i32, _i32, _dp]),
+    "netrep_ScaleFreeBins": (_int, [_dp, _i64, _i32, _i32p]),
+    "netrep_SftPowerEstimate": (_int, [_dp, _i32, C.c_double, _dp]),
+    "netrep_PickSoftThreshold": (_int, [_dp, _i32, _i32, _i64, _i64, _dp, _i32, C.c_double, _i32, _i32, _dp, _dp,
+                                        _dp]),
 }
 NR_DEBUG_SWEEP_MAX_OCC = 1
 NR_DEBUG_FAIL_SWEEP_ALLOC = 2

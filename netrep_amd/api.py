@@ -517,6 +517,58 @@ def BuildNetwork(data, beta: float, networkType: str = "unsigned", scaleData: bo
     return RMatrix(corr, m.colnames, m.colnames), RMatrix(net, m.colnames, m.colnames)
 
 
+# pickSoftThreshold's default powerVector: c(1:10, seq(12, 20, by = 2))
+DEFAULT_POWERS = tuple(range(1, 11)) + tuple(range(12, 21, 2))
+# the columns of its fitIndices table, in order
+SFT_COLUMNS = ["Power", "SFT.R.sq", "slope", "truncated.R.sq", "mean.k.", "median.k.", "max.k."]
+
+
+def ScaleFreeFit(k, nBreaks: int = 10, removeFirst: bool = False) -> dict:
+    """WGCNA's scaleFreeFitIndex of one connectivity vector (netrep_ScaleFreeFit;
+    host only, no GPU): ``{"Rsquared.SFT", "slope.SFT", "truncatedExponentialAdjRsquared"}``.
+    All NaN for a constant or non-finite ``k``."""
+    v = np.ascontiguousarray(k, dtype=np.float64).ravel()
+    out = np.empty(3)
+    L.check_api(L.load().netrep_ScaleFreeFit(_dptr(v), v.size, int(nBreaks), int(bool(removeFirst)), _dptr(out)))
+    return {"Rsquared.SFT": float(out[0]), "slope.SFT": float(out[1]),
+            "truncatedExponentialAdjRsquared": float(out[2])}
+
+
+def PickSoftThreshold(data, powerVector=DEFAULT_POWERS, networkType: str = "unsigned", corType: str = "pearson",
+                      scaleData: bool = True, RsquaredCut: float = 0.85, nBreaks: int = 10,
+                      removeFirst: bool = False, returnConnectivity: bool = False) -> dict:
+    """WGCNA's pickSoftThreshold from the data matrix alone
+    (netrep_PickSoftThreshold): ``data`` (samples x nodes, raw unless
+    ``scaleData=False``) is the only upload; the connectivities of every
+    candidate power are summed on the GPU without an n x n matrix anywhere,
+    and the scale-free fit of each runs on the host. Returns
+    ``{"powerEstimate": the first power with -sign(slope) SFT.R.sq >
+    RsquaredCut or None, "fitIndices": {column: array}}`` (columns
+    ``SFT_COLUMNS``), plus ``"connectivity"`` (nodes x powers) with
+    ``returnConnectivity``. Raises ``NetRepError`` (``NR_ERR_NONFINITE``) for
+    a constant column."""
+    m = data if isinstance(data, RMatrix) else RMatrix(np.asarray(data))
+    x = m.f
+    if x.ndim != 2:
+        raise L.NetRepError(L.NR_ERR_INVALID, "data must be a samples x nodes matrix")
+    s, n = x.shape
+    p = np.ascontiguousarray(np.atleast_1d(powerVector), dtype=np.float64)
+    if p.ndim != 1:
+        raise L.NetRepError(L.NR_ERR_INVALID, "powerVector must be a vector")
+    table = np.empty((p.size, len(SFT_COLUMNS)), order="F")
+    est = C.c_double()
+    k = np.empty((n, p.size), order="F") if returnConnectivity else None
+    L.check_api(L.load().netrep_PickSoftThreshold(
+        _dptr(x), int(bool(scaleData)), L.net_type_code(networkType, False, corType), s, n, _dptr(p), int(p.size),
+        float(RsquaredCut), int(nBreaks), int(bool(removeFirst)), _dptr(table), C.cast(C.byref(est), L._dp),
+        _dptr(k)))
+    out = {"powerEstimate": None if np.isnan(est.value) else float(est.value),
+           "fitIndices": {c: table[:, i].copy() for i, c in enumerate(SFT_COLUMNS)}}
+    if returnConnectivity:
+        out["connectivity"] = k
+    return out
+
+
 def PermutationProcedureNoData(discProps: dict, tCorr: RMatrix, tNet: RMatrix, moduleAssignments,
                                modules, nPermutations: int, nCores: int = 1,
                                nullHypothesis: str = "overlap", verbose: bool = False,

@@ -437,6 +437,118 @@ int nr_set_dataset_from_data(nr_ctx* ctx, const double* data, int64_t n_nodes, i
   });
 }
 
+int nr_soft_connectivity(nr_ctx* ctx, const double* data, int64_t n_nodes, int64_t n_samples, int scale,
+                         int net_type, const double* powers, int n_powers, double* k_out) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (!data || !powers || !k_out) return fail(ctx, NR_ERR_INVALID, "data, powers or k_out missing");
+  if (n_nodes < 1 || n_samples < 2) return fail(ctx, NR_ERR_INVALID, "data needs n_nodes >= 1 and n_samples >= 2");
+  if (n_powers < 1 || n_powers > nr::kSftMaxPowers)
+    return fail(ctx, NR_ERR_INVALID, "n_powers must be 1 .. " + std::to_string(nr::kSftMaxPowers));
+  for (int m = 0; m < n_powers; ++m)
+    if (!std::isfinite(powers[m]) || powers[m] <= 0.0) return fail(ctx, NR_ERR_INVALID, "powers must be finite and > 0");
+  const int cor_type = net_type & (NR_COR_SPEARMAN | NR_COR_BICOR);
+  const int base_type = net_type & ~(NR_COR_SPEARMAN | NR_COR_BICOR);
+  if (net_type & NR_NET_TOM) return fail(ctx, NR_ERR_INVALID, "NR_NET_TOM has no soft-threshold connectivity");
+  if (base_type != NR_NET_UNSIGNED && base_type != NR_NET_SIGNED && base_type != NR_NET_SIGNED_HYBRID)
+    return fail(ctx, NR_ERR_INVALID, "unknown network type");
+  if (cor_type == (NR_COR_SPEARMAN | NR_COR_BICOR)) return fail(ctx, NR_ERR_INVALID, "unknown correlation type");
+  if (n_nodes > (int64_t)INT32_MAX) return fail(ctx, NR_ERR_UNSUPPORTED, "n_nodes exceeds 2^31-1");
+  NR_HIP(ctx, hipSetDevice(ctx->device));
+  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // Everything on the device lives for this call only: the scaled block in a
+  // Dataset of its own (never the context's), the correlation-type scratch,
+  // the partial sums with the result behind them, two events.
+  struct Transient {
+    Dataset ds;
+    double *cor = nullptr, *sft = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    ~Transient() {
+      dfree(ds.d_data);
+      dfree(cor);
+      dfree(sft);
+      for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } t;
+  auto oom = [&](const char* what, size_t bytes, const char* formula) {
+    (void)hipGetLastError();
+    return fail(ctx, NR_ERR_OOM,
+                std::string("soft connectivity: allocation of the ") + std::to_string(bytes) + "-byte (" +
+                    std::to_string(bytes >> 20) + " MiB) " + what + " failed (" + formula + ")");
+  };
+  try {
+    const size_t block_bytes = (size_t)n_samples * (size_t)(n_nodes + 2) * sizeof(double);
+    int rc = load_data_block(ctx, t.ds, n_nodes, n_samples, scale != 0,
+                             [&](double* dst) { return put_data(ctx, data, n_samples * n_nodes, NR_HOST, dst); });
+    if (rc == NR_ERR_OOM) return oom("data block", block_bytes, "8 S (n + 2) bytes, and 8 S n more while it is scaled");
+    if (rc) return rc;
+    if (cor_type) {
+      const size_t cor_bytes = nr::cor_scratch_bytes(n_nodes, n_samples, cor_type);
+      if (hipMalloc((void**)&t.cor, cor_bytes) != hipSuccess) {
+        t.cor = nullptr;
+        return oom("correlation-type scratch", cor_bytes,
+                   cor_type == NR_COR_SPEARMAN ? "8 S (n + 2) + 8 S n bytes" : "8 S (n + 2) bytes");
+      }
+    }
+    const int R = ctx->sft_row_groups ? ctx->sft_row_groups : nr::sft_row_groups(n_nodes);
+    const size_t sft_bytes = nr::sft_scratch_bytes(n_nodes, n_powers, R);
+    if (hipMalloc((void**)&t.sft, sft_bytes) != hipSuccess) {
+      t.sft = nullptr;
+      return oom("partial sums and result", sft_bytes, "8 R P n + 8 P n bytes");
+    }
+    for (hipEvent_t& x : t.ev) NR_HIP(ctx, hipEventCreate(&x));
+    const double* const from = cor_type ? t.cor : t.ds.d_data;
+    rc = read_flags(ctx, t.ds, "soft connectivity", [&](int* flag) {
+      hipError_t p = hipSuccess;
+      if (cor_type) p = nr::launch_cor_transform(t.ds.d_data, n_samples, n_nodes, cor_type, t.cor, ctx->stream);
+      if (p == hipSuccess) p = hipEventRecord(t.ev[0], ctx->stream);
+      if (p == hipSuccess)
+        p = nr::launch_soft_connectivity(from, n_samples, n_nodes, base_type, powers, n_powers, R, t.sft, flag,
+                                         ctx->stream);
+      if (p == hipSuccess) p = hipEventRecord(t.ev[1], ctx->stream);
+      if (p == hipSuccess)
+        p = hipMemcpyAsync(k_out, t.sft + nr::sft_result_offset(n_nodes, n_powers, R),
+                           (size_t)n_nodes * (size_t)n_powers * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+      return p;
+    });
+    if (rc) {
+      (void)hipStreamSynchronize(ctx->stream);  // nothing queued still reads what is freed on return
+      return rc;
+    }
+    float ms = 0.f;
+    NR_HIP(ctx, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+    ctx->sft_ms = (double)ms;
+    ctx->sft_finite = t.ds.net_finite;
+    return NR_OK;
+  } catch (const std::bad_alloc&) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return fail(ctx, NR_ERR_OOM, "host memory allocation failed");
+  } catch (const std::exception& ex) {
+    (void)hipStreamSynchronize(ctx->stream);
+    return fail(ctx, NR_ERR_INVALID, std::string("internal error: ") + ex.what());
+  }
+}
+
+int nr_sft_ms(nr_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return NR_ERR_INVALID;
+  *ms = ctx->sft_ms;
+  return NR_OK;
+}
+
+int nr_sft_finite(nr_ctx* ctx, int* finite) {
+  if (!ctx || !finite) return NR_ERR_INVALID;
+  *finite = ctx->sft_finite;
+  return NR_OK;
+}
+
+int nr_set_sft_row_groups(nr_ctx* ctx, int row_groups) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (row_groups < 0 || row_groups > nr::kSftRowGroupsLimit)
+    return fail(ctx, NR_ERR_INVALID, "row groups must be 0 (the default) .. " + std::to_string(nr::kSftRowGroupsLimit));
+  ctx->sft_row_groups = row_groups;
+  return NR_OK;
+}
+
 int nr_set_dataset_files(nr_ctx* ctx, const char* corr_path, const char* net_path, const char* data_path,
                          const char* corr_object, const char* net_object, const char* data_object,
                          int scale_data) {

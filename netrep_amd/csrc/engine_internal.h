@@ -44,6 +44,10 @@ struct nr_ctx {
   int host_threads = 8;  // host threads of this context's staging copies (nr_ctx_set_host_threads)
 
   Dataset ds;
+  // nr_soft_connectivity (it touches nothing of the resident dataset)
+  double sft_ms = 0.0;           // device time of the last call's kernels (0: none yet)
+  int sft_finite = 1;            // the last call's connectivities were all finite
+  int sft_row_groups = 0;        // nr_set_sft_row_groups (0: the default, nr::sft_row_groups(n))
   int64_t table_checked = -1;    // modules_serial the Gram-table decision was made for
   int64_t data_gen = 0;          // bumped by every dataset change (reset_dataset)
   int64_t modules_gen = -1;      // data_gen the modules were validated against

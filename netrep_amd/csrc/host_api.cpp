@@ -26,6 +26,7 @@
 
 #include "../../include/netrep_gpu.h"
 #include "rds_reader.h"
+#include "sft_fit.h"
 
 namespace {
 
@@ -833,6 +834,71 @@ int netrep_BuildNetwork(const double* data, int32_t scale_data, int32_t net_type
   if (rc) rc = ctx_err(rc, ctx.get());
   give_ctx(ctx);
   return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_ScaleFreeFit(const double* k, int64_t n, int32_t n_breaks, int32_t remove_first, double* out3) try {
+  if (!k || !out3 || n < 1 || n_breaks < 3)
+    return set_err(NR_ERR_INVALID, "invalid arguments to ScaleFreeFit (k, out3, n >= 1, n_breaks >= 3)");
+  nr::scale_free_fit(k, n, n_breaks, remove_first != 0, out3);
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+}
+
+int netrep_ScaleFreeBins(const double* k, int64_t n, int32_t n_breaks, int32_t* bins_out) {
+  if (!k || !bins_out || n < 1 || n_breaks < 3)
+    return set_err(NR_ERR_INVALID, "invalid arguments to ScaleFreeBins (k, bins_out, n >= 1, n_breaks >= 3)");
+  (void)nr::scale_free_bins(k, n, n_breaks, bins_out, nullptr, nullptr);
+  return NR_OK;
+}
+
+int netrep_SftPowerEstimate(const double* table, int32_t n_powers, double rsquared_cut, double* power_estimate_out) {
+  if (!table || !power_estimate_out || n_powers < 1 || std::isnan(rsquared_cut))
+    return set_err(NR_ERR_INVALID, "invalid arguments to SftPowerEstimate");
+  *power_estimate_out = nr::sft_power_estimate(table, n_powers, rsquared_cut);
+  return NR_OK;
+}
+
+int netrep_PickSoftThreshold(const double* data, int32_t scale_data, int32_t net_type, int64_t n_samples,
+                             int64_t n_nodes, const double* powers, int32_t n_powers, double rsquared_cut,
+                             int32_t n_breaks, int32_t remove_first, double* table_out,
+                             double* power_estimate_out, double* connectivity_out) try {
+  // every check before a context is opened (those of nr_soft_connectivity restated)
+  if (!data || !powers || !table_out || !power_estimate_out)
+    return set_err(NR_ERR_INVALID, "data, powers, table_out or power_estimate_out missing");
+  if (n_powers < 1 || n_powers > 32) return set_err(NR_ERR_INVALID, "n_powers must be 1 .. 32");
+  for (int32_t m = 0; m < n_powers; ++m)
+    if (!std::isfinite(powers[m]) || powers[m] <= 0.0)
+      return set_err(NR_ERR_INVALID, "powers must be finite and > 0");
+  if (net_type & NR_NET_TOM) return set_err(NR_ERR_INVALID, "NR_NET_TOM has no soft-threshold connectivity");
+  if (int rc = check_from_data_args(data, net_type, 1.0, n_samples, n_nodes)) return rc;
+  if (n_breaks < 3) return set_err(NR_ERR_INVALID, "n_breaks must be >= 3");
+  if (std::isnan(rsquared_cut)) return set_err(NR_ERR_INVALID, "rsquared_cut is NaN");
+  std::vector<double> own;
+  double* k = connectivity_out;
+  if (!k) {
+    own.resize((size_t)n_nodes * (size_t)n_powers);
+    k = own.data();
+  }
+  CtxPtr ctx;
+  int rc = open_ctx(0, ctx);
+  if (rc) return rc;
+  rc = nr_soft_connectivity(ctx.get(), data, n_nodes, n_samples, scale_data, net_type, powers, n_powers, k);
+  int finite = 1;
+  if (!rc) rc = nr_sft_finite(ctx.get(), &finite);
+  if (rc) rc = ctx_err(rc, ctx.get());
+  give_ctx(ctx);
+  if (rc) return rc;
+  if (!finite) return set_err(NR_ERR_NONFINITE, "matrices cannot have non-finite or missing values");
+  for (int32_t m = 0; m < n_powers; ++m)
+    nr::sft_table_row(powers[m], k + (size_t)m * (size_t)n_nodes, n_nodes, n_breaks, remove_first != 0,
+                      table_out + m, n_powers);
+  *power_estimate_out = nr::sft_power_estimate(table_out, n_powers, rsquared_cut);
+  return NR_OK;
 } catch (const std::bad_alloc&) {
   return set_err(NR_ERR_OOM, "host memory allocation failed");
 } catch (const std::exception& e) {

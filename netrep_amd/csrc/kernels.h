@@ -207,6 +207,32 @@ int cor_cols_per_workgroup(int64_t S);
 size_t cor_scratch_bytes(int64_t n, int64_t S, int cor_type);
 hipError_t launch_cor_transform(const double* X, int64_t S, int64_t n, int cor_type, double* scratch,
                                 hipStream_t st);
+// The soft-threshold connectivities (netbuild.hip, nr_soft_connectivity):
+// k[j + m n] = sum over i != j of b_ij^powers[m], b the base of net_type
+// (|c|, (1 + c) / 2, or c where c > 0 else 0) of c = clamp(x_i . x_j / (S - 1),
+// -1, 1), from the block X that launch_netbuild takes; no n x n array exists.
+// soft_connectivity_kernel: one workgroup per (column tile, row group) walks
+// its row tiles through the SYRK main loop and keeps one running sum per
+// distinct power and column in registers; it writes part[r][slot][j]. A second
+// kernel adds the row groups in increasing r. No floating-point atomics: k
+// depends on n and the row-group count alone, never on the grid's schedule.
+// All powers integers <= kSftMaxChain: one multiplication chain b, b^2, ...
+// per element; otherwise one pow per element and distinct power. A launch
+// holds 16 distinct powers on the chain path, 8 on the pow path; more run
+// another sweep of the matrix into the same partials. row_groups
+// 0: sft_row_groups(n). scratch: sft_scratch_bytes(n, P, R) bytes, the
+// partials (8 R P n) and k (8 P n) behind them; the result is at
+// scratch + sft_result_offset(n, P, R) doubles. flags |= 4 for a non-finite k.
+constexpr int kSftMaxPowers = 32;
+constexpr int kSftMaxChain = 64;
+constexpr int kSftTilesPerGroup = 16;   // row tiles a workgroup walks by default
+constexpr int kSftMaxRowGroups = 32;    // default row groups at most (bounds the partials)
+constexpr int kSftRowGroupsLimit = 1024;  // largest row-group count the test override takes
+int sft_row_groups(int64_t n);
+size_t sft_result_offset(int64_t n, int n_powers, int row_groups);
+size_t sft_scratch_bytes(int64_t n, int n_powers, int row_groups);
+hipError_t launch_soft_connectivity(const double* X, int64_t S, int64_t n, int net_type, const double* powers,
+                                    int n_powers, int row_groups, double* scratch, int* flags, hipStream_t st);
 // corr[e], net[e] (either may be NULL) = elements [first, first + len) of a
 // pair array in layout es (1, or 2: the Gram table).
 hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,

@@ -15,6 +15,10 @@
 // stores go through an LDS image of half the tile so that each wave
 // instruction writes 16 bytes per lane along contiguous rows of the
 // column-major array: neither store is strided by n.
+//
+// tom_kernel (NR_NET_TOM) and soft_connectivity_kernel (nr_soft_connectivity:
+// the soft-threshold connectivities, no n x n array stored) run the same main
+// loop, nb_syrk_tile, with epilogues of their own; see there.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <math.h>
@@ -388,6 +392,177 @@ tom_kernel(const double* __restrict__ A, const double* __restrict__ k, int64_t n
   if (bad && lane == 0) atomicOr(flags, bad);
 }
 
+// ---- soft-threshold connectivities (nr_soft_connectivity) -------------------
+//
+// The distinct powers of a call in ascending order are its "slots";
+// slot_of[m] is the slot of the caller's m-th power (duplicates share one). A
+// launch of soft_connectivity_kernel takes up to kSftChainSlots (chain path)
+// or kSftPowSlots (pow path: that many inlined pows fit the register budget
+// of two workgroups per CU without a spill) of them, slots slot0 .. slot0 +
+// n_slots - 1 of n_slots_total, one running sum in registers each: for the
+// chain path step[s] is the number of multiplications by b that lead from the
+// launch's slot s - 1 (from b itself for s = 0) to slot s; for the pow path
+// p[s] is the power.
+constexpr int kSftChainSlots = 16;
+constexpr int kSftPowSlots = 8;
+constexpr int kSftLaunchSlots = kSftChainSlots > kSftPowSlots ? kSftChainSlots : kSftPowSlots;
+struct SftPowers {
+  int n_slots, slot0, n_slots_total;
+  int step[kSftLaunchSlots];
+  double p[kSftLaunchSlots];
+};
+struct SftSlots {
+  int slot_of[kSftMaxPowers];
+};
+
+// c of the SYRK's g as netbuild_kernel's epilogue computes it, and the base b
+// the powers are taken of: NaN in, NaN out (the hybrid's test is false for NaN).
+__device__ __forceinline__ double sft_base(double g, double denom, int net_type) {
+  double c = g / denom;
+  c = c > 1.0 ? 1.0 : (c < -1.0 ? -1.0 : c);  // R's cor clamps; NaN stays NaN
+  return net_type == NR_NET_UNSIGNED ? fabs(c) : (net_type == NR_NET_SIGNED ? (1.0 + c) * 0.5 : (c <= 0.0 ? 0.0 : c));
+}
+
+constexpr int kSftRows = kNbTile / 4;   // rows of a tile per thread: wave w owns rows 16 w .. 16 w + 15
+constexpr int kSftBatch = 8;            // of which the chain path holds this many in registers at a time
+static_assert(kNbTile * kNbOutLd <= kNbPanelDoubles, "the whole tile's g is staged in the panels' LDS");
+static_assert(4 * kSftLaunchSlots * kNbTile <= kNbPanelDoubles, "so are the four partial sums per slot and column");
+static_assert(kSftChainSlots % 4 == 0 && kSftPowSlots % 4 == 0,
+              "the strip-end combine gives every thread slots / 4 sums to finish");
+
+// soft_connectivity_kernel: workgroup (J, r) = blockIdx.(x, y) owns columns
+// 64 J .. 64 J + 63 and the row tiles [r tiles_per_group, (r + 1)
+// tiles_per_group) of the FULL matrix (not the lower triangle: twice the SYRK
+// flops, for no n^2 scratch and no dependency between tiles). Per tile: the
+// SYRK main loop, g staged whole in LDS as stage[j][i] (kNbOutLd per column),
+// then thread (wave w, lane l) reads rows 16 w .. 16 w + 15 of column l --
+// the column index is in the lane, so the odd stride is conflict-free -- and
+// adds b^p to its n_slots running sums, in increasing row order. Rows and
+// columns past n and the diagonal enter as b = 0 (a select: a NaN there must
+// not leak), which adds +0 for every power > 0. At the strip's end the four
+// threads of a column add up in wave order and part[(r n_slots_total + slot0
+// + s) n + j] is written with plain stores, 64 consecutive j per wave
+// instruction. A group without row tiles writes zeros.
+template <bool CHAIN>
+__global__ void __launch_bounds__(256, 2)
+soft_connectivity_kernel(const double* __restrict__ X, int64_t S, int64_t n, int net_type, SftPowers pw,
+                         int64_t tiles_per_group, double* __restrict__ part) {
+  __shared__ __attribute__((aligned(16))) double lds[kNbPanelDoubles];
+  double* const pA = lds;
+  double* const pB = lds + kNbTile * kNbLd;
+  double* const stage = lds;  // [64 columns j][kNbOutLd rows i]
+  // the slots' steps / powers, read where they are used (by value they would
+  // sit in scalar registers for the whole kernel)
+  __shared__ double slot_p[kSftLaunchSlots];
+  __shared__ int slot_step[kSftLaunchSlots];
+  if (threadIdx.x < kSftLaunchSlots) {
+    slot_p[threadIdx.x] = pw.p[threadIdx.x];
+    slot_step[threadIdx.x] = pw.step[threadIdx.x];
+  }
+  __syncthreads();
+  const int n_slots = pw.n_slots;
+  constexpr int NS = CHAIN ? kSftChainSlots : kSftPowSlots;
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i16 = lane & 15, kk = lane >> 4;
+  const int wr = wave & 1, wc = wave >> 1;
+  const int64_t nT = (n + kNbTile - 1) / kNbTile;
+  const int64_t zero_col = (n + 1) * S;
+  const double denom = (double)(S - 1);
+  const int64_t J = blockIdx.x, r = blockIdx.y;
+  const int64_t gj = J * kNbTile + lane;
+  const int64_t I0 = r * tiles_per_group;
+  const int64_t I1 = I0 + tiles_per_group < nT ? I0 + tiles_per_group : nT;
+
+  double sum[NS];
+#pragma unroll
+  for (int s = 0; s < NS; ++s) sum[s] = 0.0;
+
+  for (int64_t I = I0; I < I1; ++I) {
+    nb_f64x4 acc[2][2];
+    nb_syrk_tile(X, S, n, zero_col, I, J, pA, pB, wr, wc, i16, kk, acc);
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          // D[row = (lane >> 4) + 4 q][col = lane & 15] (f64 MFMA C/D map)
+          stage[(32 * wc + 16 * b + i16) * kNbOutLd + 32 * wr + 16 * a + kk + 4 * q] = acc[a][b][q];
+    __syncthreads();
+    const double* const col = stage + lane * kNbOutLd + kSftRows * wave;
+    const int64_t gi0 = I * kNbTile + kSftRows * wave;
+    if (CHAIN) {
+#pragma unroll 1
+      for (int h = 0; h < kSftRows / kSftBatch; ++h) {
+        double b[kSftBatch], v[kSftBatch];
+#pragma unroll
+        for (int q = 0; q < kSftBatch; ++q) {
+          const int64_t gi = gi0 + kSftBatch * h + q;
+          const double x = sft_base(col[kSftBatch * h + q], denom, net_type);
+          b[q] = gi < n && gj < n && gi != gj ? x : 0.0;
+          v[q] = b[q];
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          if (s < n_slots) {
+            const int steps = __builtin_amdgcn_readfirstlane(slot_step[s]);
+            for (int t = 0; t < steps; ++t) {
+#pragma unroll
+              for (int q = 0; q < kSftBatch; ++q) v[q] *= b[q];
+            }
+#pragma unroll
+            for (int q = 0; q < kSftBatch; ++q) sum[s] += v[q];
+          }
+        }
+      }
+    } else {
+#pragma unroll 1
+      for (int q = 0; q < kSftRows; ++q) {
+        const int64_t gi = gi0 + q;
+        const double x = sft_base(col[q], denom, net_type);
+        const double b = gi < n && gj < n && gi != gj ? x : 0.0;
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+          if (s < n_slots) sum[s] += pow(b, slot_p[s]);
+      }
+    }
+    __syncthreads();  // the stage is free for the next tile's panels
+  }
+
+  // the four threads of a column, in wave order: lds[wave][slot][column]
+#pragma unroll
+  for (int s = 0; s < NS; ++s) lds[(wave * NS + s) * kNbTile + lane] = sum[s];
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < NS / 4; ++t) {
+    const int s = wave + 4 * t;
+    const double* const q = lds + s * kNbTile + lane;
+    constexpr int kWave = NS * kNbTile;
+    const double total = ((q[0] + q[kWave]) + q[2 * kWave]) + q[3 * kWave];
+    if (s < n_slots && gj < n) part[((int64_t)r * pw.n_slots_total + pw.slot0 + s) * n + gj] = total;
+  }
+}
+
+// k[j + m n] = the sum over the row groups, in increasing r, of the partials
+// of power m's slot; blockIdx.y = m. flags |= 4 for a non-finite k.
+__global__ void __launch_bounds__(256)
+soft_connectivity_reduce_kernel(const double* __restrict__ part, int64_t n, int row_groups, int n_slots, SftSlots sl,
+                                double* __restrict__ k, int* __restrict__ flags) {
+  const int m = blockIdx.y;
+  const double* const src = part + (int64_t)sl.slot_of[m] * n;
+  int bad = 0;
+  for (int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+    double t = 0.0;
+    for (int r = 0; r < row_groups; ++r) t += src[(int64_t)r * n_slots * n + j];
+    k[j + (int64_t)m * n] = t;
+    bad |= isfinite(t) ? 0 : 4;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bad |= __shfl_xor(bad, o, 64);
+  if (bad && (threadIdx.x & 63) == 0) atomicOr(flags, bad);
+}
+
 // corr[e] / net[e] of elements [first, first + len) of a pair array with
 // element stride es (1: {corr, net}; 2: the Gram-table layout).
 __global__ void deinterleave_kernel(const double2* __restrict__ pairs, int es, int64_t first, int64_t len,
@@ -425,6 +600,67 @@ hipError_t launch_tom(int64_t n, double2* pairs, double* scratch, int* flags, hi
   const int64_t n_tiles = nT * (nT + 1) / 2;
   const unsigned g = (unsigned)std::min<int64_t>(n_tiles, (int64_t)1 << 20);
   hipLaunchKernelGGL(tom_kernel, dim3(g), dim3(256), 0, st, A, k, n, pairs, flags);
+  return hipGetLastError();
+}
+
+// A pure function of n and compile-time constants (never of the device): k
+// is the same bits wherever it is computed.
+int sft_row_groups(int64_t n) {
+  const int64_t nT = (n + kNbTile - 1) / kNbTile;
+  return (int)std::min<int64_t>((nT + kSftTilesPerGroup - 1) / kSftTilesPerGroup, kSftMaxRowGroups);
+}
+
+size_t sft_result_offset(int64_t n, int n_powers, int row_groups) {
+  return (size_t)row_groups * (size_t)n_powers * (size_t)n;
+}
+
+size_t sft_scratch_bytes(int64_t n, int n_powers, int row_groups) {
+  return (sft_result_offset(n, n_powers, row_groups) + (size_t)n_powers * (size_t)n) * sizeof(double);
+}
+
+hipError_t launch_soft_connectivity(const double* X, int64_t S, int64_t n, int net_type, const double* powers,
+                                    int n_powers, int row_groups, double* scratch, int* flags, hipStream_t st) {
+  if (n_powers < 1 || n_powers > kSftMaxPowers || row_groups < 0 || row_groups > kSftRowGroupsLimit)
+    return hipErrorInvalidValue;
+  const int R = row_groups ? row_groups : sft_row_groups(n);
+  bool chain = true;
+  for (int m = 0; m < n_powers; ++m)
+    chain = chain && powers[m] >= 1.0 && powers[m] <= (double)kSftMaxChain && powers[m] == floor(powers[m]);
+  // the distinct powers, ascending
+  double distinct[kSftMaxPowers];
+  std::copy(powers, powers + n_powers, distinct);
+  std::sort(distinct, distinct + n_powers);
+  const int n_slots = (int)(std::unique(distinct, distinct + n_powers) - distinct);
+  SftSlots sl = {};
+  for (int m = 0; m < n_powers; ++m)
+    sl.slot_of[m] = (int)(std::lower_bound(distinct, distinct + n_slots, powers[m]) - distinct);
+
+  const int64_t nT = (n + kNbTile - 1) / kNbTile;
+  const int64_t tiles_per_group = (nT + R - 1) / R;
+  double* const part = scratch;
+  double* const k = scratch + sft_result_offset(n, n_powers, R);
+  const dim3 grid((unsigned)nT, (unsigned)R);
+  const int per_launch = chain ? kSftChainSlots : kSftPowSlots;
+  for (int s0 = 0; s0 < n_slots; s0 += per_launch) {  // more distinct powers than a launch takes: another sweep
+    SftPowers pw = {};
+    pw.n_slots = std::min(per_launch, n_slots - s0);
+    pw.slot0 = s0;
+    pw.n_slots_total = n_slots;
+    for (int s = 0; s < pw.n_slots; ++s) {
+      pw.p[s] = distinct[s0 + s];
+      pw.step[s] = chain ? (int)distinct[s0 + s] - (s ? (int)distinct[s0 + s - 1] : 1) : 0;
+    }
+    if (chain)
+      hipLaunchKernelGGL(soft_connectivity_kernel<true>, grid, dim3(256), 0, st, X, S, n, net_type, pw,
+                         tiles_per_group, part);
+    else
+      hipLaunchKernelGGL(soft_connectivity_kernel<false>, grid, dim3(256), 0, st, X, S, n, net_type, pw,
+                         tiles_per_group, part);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const dim3 rgrid((unsigned)std::min<int64_t>((n + 255) / 256, 4096), (unsigned)n_powers);
+  hipLaunchKernelGGL(soft_connectivity_reduce_kernel, rgrid, dim3(256), 0, st, part, n, R, n_slots, sl, k, flags);
   return hipGetLastError();
 }
 

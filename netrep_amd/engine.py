@@ -41,6 +41,8 @@ class Engine:
     # quarter of it (COR_WAVE_ROWS) a wave owns a column, four per workgroup.
     COR_LDS_ROWS = 2048
     COR_WAVE_ROWS = COR_LDS_ROWS // 4
+    # candidate powers one soft_connectivity call takes (kSftMaxPowers, csrc/kernels.h)
+    SFT_MAX_POWERS = 32
 
     def __init__(self, device: int = 0):
         self._lib = L.load()
@@ -153,6 +155,42 @@ class Engine:
         ms = C.c_double()
         self._check(self._lib.nr_cor_ms(self._h, C.byref(ms)))
         return float(ms.value)
+
+    def soft_connectivity(self, data, powers, net_type="unsigned", scale=True, cor_type="pearson"):
+        """The soft-threshold connectivities of WGCNA's pickSoftThreshold from
+        the data matrix alone (S x N, host numpy; nr_soft_connectivity): an
+        ``(N, len(powers))`` Fortran-ordered array, column m holding
+        ``k_i = sum_{u != i} b_iu ** powers[m]`` with b the base of
+        ``net_type`` (|cor|, (1 + cor) / 2, or cor where cor > 0 else 0) and
+        cor of ``cor_type``. No N x N matrix exists on the host or the device,
+        and the engine's resident dataset and modules are not touched. A
+        constant column makes every connectivity NaN (no error here;
+        ``PickSoftThreshold`` raises). At most ``SFT_MAX_POWERS`` powers,
+        finite and > 0; order and duplicates are kept."""
+        d = _f64(data)
+        if d.ndim != 2:
+            raise ValueError("data must be a samples x nodes matrix")
+        s, n = d.shape
+        p = np.ascontiguousarray(np.atleast_1d(powers), dtype=np.float64)
+        if p.ndim != 1:
+            raise ValueError("powers must be a vector")
+        k = np.empty((n, p.size), dtype=np.float64, order="F")
+        self._check(self._lib.nr_soft_connectivity(self._h, _ptr(d), n, s, int(bool(scale)),
+                                                   L.net_type_code(net_type, False, cor_type), _ptr(p),
+                                                   int(p.size), _ptr(k)))
+        return k
+
+    def sft_ms(self) -> float:
+        """Device time in ms of the two kernels of this engine's last
+        ``soft_connectivity`` call (nr_sft_ms), 0 before the first."""
+        ms = C.c_double()
+        self._check(self._lib.nr_sft_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def set_sft_row_groups(self, row_groups: int):
+        """Test knob (nr_set_sft_row_groups): the row-group count of later
+        ``soft_connectivity`` calls; 0 restores the default."""
+        self._check(self._lib.nr_set_sft_row_groups(self._h, int(row_groups)))
 
     def set_dataset_files(self, corr_path, net_path, data_path=None, objects=(None, None, None),
                           scale_data=True):
