@@ -680,6 +680,75 @@ void netrep_ReleaseResident(void);
 int netrep_PoolInfo(int64_t* n_pooled, int64_t* scratch_bytes, int32_t* host_threads_min,
                     int32_t* host_threads_max);
 
+/* A from-data dataset kept resident and used in every role: discovery
+ * properties, network properties and the permutation test, with one upload
+ * and one build. The handle owns a context on GPU 0 that holds the scaled
+ * data and the {correlation, network} built from them
+ * (nr_set_dataset_from_data; 16 n^2 + 8 S (n + 2) bytes of HBM, 40 n^2 while a
+ * permutation run's Gram table stands in for the pair array), and a copy of
+ * the node names. A handle is used by one thread at a time: concurrent calls
+ * on one handle are serialised by a mutex in the handle. netrep_ReleaseResident
+ * does NOT free live handles (their contexts are not pooled); only
+ * netrep_DatasetRelease does. */
+typedef struct netrep_dataset netrep_dataset;
+
+/* Build the handle. The argument checks of the other from-data entries run
+ * before any context is opened (same messages). net_type takes NR_NET_TOM and
+ * the NR_COR_* bits as everywhere else. A correlation or network that is not
+ * all finite (a constant column) returns NR_ERR_NONFINITE with CheckFinite's
+ * message: no handle is returned and the context goes back to the pool. On
+ * NR_ERR_OOM what is held between calls is released (netrep_ReleaseResident)
+ * and the build tried once more. n_cores: the host threads of the upload (0:
+ * the process-wide count). */
+int netrep_DatasetFromData(const double* data, int32_t scale_data, int32_t net_type, double beta,
+                           int64_t n_samples, int64_t n_nodes, const char* const* node_names,
+                           int32_t n_cores, netrep_dataset** out);
+/* Free the dataset; its context goes back to the pool. NULL is a no-op. */
+void netrep_DatasetRelease(netrep_dataset* d);
+/* Either output may be NULL. */
+int netrep_DatasetShape(netrep_dataset* d, int64_t* n_nodes, int64_t* n_samples);
+/* The resident matrices copied back (nr_get_dataset_matrices; n_nodes x
+ * n_nodes each, either may be NULL), whichever pair layout is resident. */
+int netrep_DatasetMatrices(netrep_dataset* d, double* corr_out, double* net_out);
+/* netrep_IntermediateProperties with the handle as the discovery dataset: its
+ * node names are the discovery names, nothing is uploaded but the module index
+ * sets, and contribution is always produced (the handle always has data). */
+int netrep_DatasetIntermediateProperties(
+    netrep_dataset* d, const char* const* t_node_names, int64_t n_t_nodes,
+    const char* const* ma_names, const char* const* ma_labels, int64_t n_assign,
+    const char* const* modules, int64_t n_modules, double* degree_out, int64_t* degree_len,
+    double* corr_out, int64_t* corr_len, double* contribution_out, int64_t* contribution_len);
+/* netrep_NetProps on the handle's network and data (the data as the handle
+ * holds them: scaled on the device if it was built with scale_data). */
+int netrep_DatasetNetProps(netrep_dataset* d, const char* const* ma_names, const char* const* ma_labels,
+                           int64_t n_assign, const char* const* modules, int64_t n_modules,
+                           double* degree_out, double* contribution_out, double* summary_out,
+                           double* coherence_out, double* avg_weight_out, int64_t* k_all_out);
+/* netrep_PermutationProcedureFromData without the build: the handle is the
+ * test dataset. The handle's dataset is resident and unchanged afterwards
+ * (whichever pair layout the run chose, after a multi-GPU broadcast, an
+ * interrupt or an error); the run's per-batch work buffers are freed. */
+int netrep_DatasetPermutationProcedure(
+    const netrep_disc_props* disc_props, netrep_dataset* d, const char* const* ma_names,
+    const char* const* ma_labels, int64_t n_assign, const char* const* modules, int64_t n_modules,
+    int64_t n_perm, int32_t n_cores, const char* null_hypothesis, int32_t verbose, uint64_t seed,
+    const uint32_t* pi, double* nulls_out, double* observed_out);
+
+/* One-shots for glue whose call sites are separate: build the handle, make
+ * the one call, release it. */
+int netrep_IntermediatePropertiesFromData(
+    const double* d_data, int32_t scale_data, int32_t net_type, double beta, int64_t n_samples,
+    int64_t n_nodes, const char* const* d_names, const char* const* t_node_names, int64_t n_t_nodes,
+    const char* const* ma_names, const char* const* ma_labels, int64_t n_assign,
+    const char* const* modules, int64_t n_modules, double* degree_out, int64_t* degree_len,
+    double* corr_out, int64_t* corr_len, double* contribution_out, int64_t* contribution_len);
+int netrep_NetPropsFromData(const double* data, int32_t scale_data, int32_t net_type, double beta,
+                            int64_t n_samples, int64_t n_nodes, const char* const* node_names,
+                            const char* const* ma_names, const char* const* ma_labels, int64_t n_assign,
+                            const char* const* modules, int64_t n_modules, double* degree_out,
+                            double* contribution_out, double* summary_out, double* coherence_out,
+                            double* avg_weight_out, int64_t* k_all_out);
+
 /* Last error of the reference-interface layer (thread-local). */
 const char* netrep_last_error(void);
 

@@ -12,6 +12,7 @@ from .api import (CheckFinite, IntermediateProperties, IntermediatePropertiesNoD
                   NetProps, NetPropsNoData, PermutationProcedure, PermutationProcedureNoData,
                   PrefetchTestDataset, DiscardPrefetch, ReleaseResident, h2d_bytes, PermutationProcedureFiles, RMatrix,
                   PermutationProcedureFromData, BuildNetwork, PickSoftThreshold, ScaleFreeFit,
+                  FromDataDataset, IntermediatePropertiesFromData, NetPropsFromData, modulePreservationFromData,
                   read_rds_matrix, Scale, STATNAMES, STATNAMES_NODATA,
                   set_interrupt_hook)
 from .engine import Engine, device_count, prp_table  # noqa: F401
@@ -21,4 +22,6 @@ __all__ = ["CheckFinite", "IntermediateProperties", "IntermediatePropertiesNoDat
            "Scale", "Engine", "NetRepError", "device_count", "prp_table", "STATNAMES",
            "STATNAMES_NODATA", "set_interrupt_hook", "PrefetchTestDataset",
            "DiscardPrefetch", "ReleaseResident", "h2d_bytes", "PermutationProcedureFiles", "read_rds_matrix",
-           "PermutationProcedureFromData", "BuildNetwork", "PickSoftThreshold", "ScaleFreeFit"]
+           "PermutationProcedureFromData", "BuildNetwork", "PickSoftThreshold", "ScaleFreeFit",
+           "FromDataDataset", "IntermediatePropertiesFromData", "NetPropsFromData",
+           "modulePreservationFromData"]

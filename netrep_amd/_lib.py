@@ -158,6 +158,21 @@ SIGNATURES = {
     "netrep_SftPowerEstimate": (_int, [_dp, _i32, C.c_double, _dp]),
     "netrep_PickSoftThreshold": (_int, [_dp, _i32, _i32, _i64, _i64, _dp, _i32, C.c_double, _i32, _i32, _dp, _dp,
                                         _dp]),
+    # netrep_dataset* travels as a void pointer
+    "netrep_DatasetFromData": (_int, [_dp, _i32, _i32, C.c_double, _i64, _i64, _strv, _i32, C.POINTER(_p)]),
+    "netrep_DatasetRelease": (None, [_p]),
+    "netrep_DatasetShape": (_int, [_p, _i64p, _i64p]),
+    "netrep_DatasetMatrices": (_int, [_p, _dp, _dp]),
+    "netrep_DatasetIntermediateProperties": (_int, [_p, _strv, _i64, _strv, _strv, _i64, _strv, _i64, _dp, _i64p,
+                                                    _dp, _i64p, _dp, _i64p]),
+    "netrep_DatasetNetProps": (_int, [_p, _strv, _strv, _i64, _strv, _i64, _dp, _dp, _dp, _dp, _dp, _i64p]),
+    "netrep_DatasetPermutationProcedure": (_int, [C.POINTER(DiscProps), _p, _strv, _strv, _i64, _strv, _i64, _i64,
+                                                  _i32, C.c_char_p, _i32, _u64, _u32p, _dp, _dp]),
+    "netrep_IntermediatePropertiesFromData": (_int, [_dp, _i32, _i32, C.c_double, _i64, _i64, _strv, _strv, _i64,
+                                                     _strv, _strv, _i64, _strv, _i64, _dp, _i64p, _dp, _i64p, _dp,
+                                                     _i64p]),
+    "netrep_NetPropsFromData": (_int, [_dp, _i32, _i32, C.c_double, _i64, _i64, _strv, _strv, _strv, _i64, _strv,
+                                       _i64, _dp, _dp, _dp, _dp, _dp, _i64p]),
 }
 NR_DEBUG_SWEEP_MAX_OCC = 1
 NR_DEBUG_FAIL_SWEEP_ALLOC = 2

@@ -98,54 +98,69 @@ def CheckFinite(mat) -> None:
     L.check_api(L.load().netrep_CheckFinite(_dptr(x2), x2.shape[0], x2.shape[1]))
 
 
+class _IntermediateCall:
+    """The module arguments and output buffers of an IntermediateProperties
+    entry (``args``: from t_node_names to contribution_len, in the C order),
+    and the unpacking of what the call wrote."""
+
+    def __init__(self, t_node_names, module_assignments, modules, with_data):
+        names, labels = _assignments(module_assignments)
+        self.modules = [str(m) for m in modules]
+        self.with_data = with_data
+        t_node_names = list(t_node_names)
+        # upper bounds for the concatenated outputs: module sizes in discovery
+        sizes = {}
+        tset = set(map(str, t_node_names))
+        for nm, lab in zip(names, labels):
+            if nm in tset:
+                sizes[lab] = sizes.get(lab, 0) + 1
+        ks = [sizes.get(m, 0) for m in self.modules]
+        self.deg = np.empty(max(sum(ks), 1))
+        self.cv = np.empty(max(sum(k * (k - 1) // 2 for k in ks), 1))
+        self.nc = np.empty(max(sum(ks), 1)) if with_data else None
+        nm_ = len(self.modules)
+        self.deg_len = np.zeros(nm_, dtype=np.int64)
+        self.cv_len = np.zeros(nm_, dtype=np.int64)
+        self.nc_len = np.zeros(nm_, dtype=np.int64)
+        tn, _k2 = _strv(t_node_names)
+        an, _k3 = _strv(names)
+        al, _k4 = _strv(labels)
+        mo, _k5 = _strv(self.modules)
+        self._keep = (_k2, _k3, _k4, _k5)
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
+        self.args = (tn, len(t_node_names), an, al, len(names), mo, nm_, _dptr(self.deg), i64(self.deg_len),
+                     _dptr(self.cv), i64(self.cv_len), _dptr(self.nc),
+                     i64(self.nc_len) if self.nc is not None else None)
+
+    def result(self) -> dict:
+        out = {"degree": {}, "corr": {}}
+        if self.with_data:
+            out["contribution"] = {}
+        od = oc = 0
+        for i, m in enumerate(self.modules):
+            if self.deg_len[i] == 0:
+                continue                                     # only modsPresent (src/discProps.cpp:123-125)
+            out["degree"][m] = self.deg[od:od + self.deg_len[i]].copy()
+            out["corr"][m] = self.cv[oc:oc + self.cv_len[i]].copy()
+            if self.with_data:
+                out["contribution"][m] = self.nc[od:od + self.nc_len[i]].copy()
+            od += self.deg_len[i]
+            oc += self.cv_len[i]
+        return out
+
+
 def _intermediate(d_data, d_corr, d_net, t_node_names, module_assignments, modules):
     lib = L.load()
-    names, labels = _assignments(module_assignments)
-    modules = [str(m) for m in modules]
     d_names = list(d_net.colnames)
     n = len(d_names)
     corr = d_corr.f
     net = d_net.f
     data = d_data.f if d_data is not None else None
     s = data.shape[0] if data is not None else 0
-    # upper bounds for the concatenated outputs: module sizes in discovery
-    sizes = {}
-    tset = set(map(str, t_node_names))
-    for nm, lab in zip(names, labels):
-        if nm in tset:
-            sizes[lab] = sizes.get(lab, 0) + 1
-    ks = [sizes.get(m, 0) for m in modules]
-    deg = np.empty(max(sum(ks), 1))
-    cv = np.empty(max(sum(k * (k - 1) // 2 for k in ks), 1))
-    nc = np.empty(max(sum(ks), 1)) if data is not None else None
-    nm_ = len(modules)
-    deg_len = np.zeros(nm_, dtype=np.int64)
-    cv_len = np.zeros(nm_, dtype=np.int64)
-    nc_len = np.zeros(nm_, dtype=np.int64)
+    call = _IntermediateCall(t_node_names, module_assignments, modules, data is not None)
     dn, _k1 = _strv(d_names)
-    tn, _k2 = _strv(t_node_names)
-    an, _k3 = _strv(names)
-    al, _k4 = _strv(labels)
-    mo, _k5 = _strv(modules)
-    i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
-    L.check_api(lib.netrep_IntermediateProperties(
-        _dptr(data), _dptr(corr), _dptr(net), s, n, dn, tn, len(t_node_names), an, al, len(names),
-        mo, nm_, _dptr(deg), i64(deg_len), _dptr(cv), i64(cv_len), _dptr(nc),
-        i64(nc_len) if nc is not None else None))
-    out = {"degree": {}, "corr": {}}
-    if data is not None:
-        out["contribution"] = {}
-    od = oc = 0
-    for i, m in enumerate(modules):
-        if deg_len[i] == 0:
-            continue                                     # only modsPresent (src/discProps.cpp:123-125)
-        out["degree"][m] = deg[od:od + deg_len[i]].copy()
-        out["corr"][m] = cv[oc:oc + cv_len[i]].copy()
-        if data is not None:
-            out["contribution"][m] = nc[od:od + nc_len[i]].copy()
-        od += deg_len[i]
-        oc += cv_len[i]
-    return out
+    L.check_api(lib.netrep_IntermediateProperties(_dptr(data), _dptr(corr), _dptr(net), s, n, dn, *call.args))
+    return call.result()
 
 
 def IntermediateProperties(dData: RMatrix, dCorr: RMatrix, dNet: RMatrix, tNodeNames,
@@ -441,6 +456,54 @@ def PermutationProcedureFiles(discProps: dict, tData_file: Optional[str], tCorr_
     return _permutation_result(rc, modules, with_data, observed, nulls, nPermutations)
 
 
+def _named_data(data, what):
+    """(node names, column-major values) of a from-data entry's data matrix."""
+    if getattr(data, "colnames", None) is None:
+        raise L.NetRepError(L.NR_ERR_INVALID, f"{what} needs colnames (the node names)")
+    names = [str(n) for n in data.colnames]
+    x = data.f
+    if x.ndim != 2 or len(names) != x.shape[1]:
+        raise L.NetRepError(L.NR_ERR_INVALID, f"{what} must have one colname per column")
+    return names, x
+
+
+class _DataPermutationCall:
+    """The arguments after the dataset of a permutation entry whose test
+    dataset has data and is named by ``t_names`` (``args``: from ma_names to
+    observed_out, in the C order), and the result of the call."""
+
+    def __init__(self, disc_props, t_names, module_assignments, modules, n_perm, n_cores, null_hypothesis,
+                 verbose, seed, pi):
+        names, labels = _assignments(module_assignments)
+        self.modules = [str(m) for m in modules]
+        self.n_perm = int(n_perm)
+        nm_ = len(self.modules)
+        self.dp, self._keep = _marshal_disc_props(disc_props, self.modules, True)
+        self.observed = np.empty((nm_, 7), order="F")
+        self.nulls = np.empty((nm_, 7, self.n_perm), order="F") if self.n_perm > 0 else None
+        pi_arr = None
+        if pi is not None:
+            pi_arr = np.ascontiguousarray(pi, dtype=np.uint32)
+            n_null = _null_pool_size(names, t_names, null_hypothesis)
+            if pi_arr.ndim != 2 or pi_arr.shape != (self.n_perm, n_null):
+                raise L.NetRepError(L.NR_ERR_INVALID, f"pi must have shape (nPermutations, n_null) = "
+                                                      f"({self.n_perm}, {n_null}), got {pi_arr.shape}")
+        self._pi = pi_arr
+        an, _k2 = _strv(names)
+        al, _k3 = _strv(labels)
+        mo, _k4 = _strv(self.modules)
+        self._strs = (_k2, _k3, _k4)
+        if verbose and not _progress_user_set:
+            _install_progress(_print_progress)
+        self.args = (an, al, len(names), mo, nm_, self.n_perm, int(n_cores), str(null_hypothesis).encode(),
+                     int(bool(verbose)), int(seed) & (2**64 - 1),
+                     pi_arr.ctypes.data_as(C.POINTER(C.c_uint32)) if pi_arr is not None else None,
+                     _dptr(self.nulls), _dptr(self.observed))
+
+    def result(self, rc) -> dict:
+        return _permutation_result(rc, self.modules, True, self.observed, self.nulls, self.n_perm)
+
+
 def PermutationProcedureFromData(discProps: dict, tData: RMatrix, beta: float, moduleAssignments, modules,
                                  nPermutations: int, nCores: int = 1, nullHypothesis: str = "overlap",
                                  verbose: bool = False, seed: int = DEFAULT_SEED, pi=None,
@@ -460,47 +523,23 @@ def PermutationProcedureFromData(discProps: dict, tData: RMatrix, beta: float, m
     ``NetRepError`` (``NR_ERR_NONFINITE``) if they are not all finite, e.g.
     for a constant column."""
     lib = L.load()
-    names, labels = _assignments(moduleAssignments)
-    modules = [str(m) for m in modules]
-    if tData.colnames is None:
-        raise L.NetRepError(L.NR_ERR_INVALID, "tData needs colnames (the node names)")
-    t_names = list(tData.colnames)
-    data = tData.f
+    t_names, data = _named_data(tData, "tData")
     s, n = data.shape
-    if len(t_names) != n:
-        raise L.NetRepError(L.NR_ERR_INVALID, "tData must have one colname per column")
-    nm_ = len(modules)
-    dp, _keep = _marshal_disc_props(discProps, modules, True)
-    observed = np.empty((nm_, 7), order="F")
-    nulls = np.empty((nm_, 7, int(nPermutations)), order="F") if nPermutations > 0 else None
-    pi_arr = None
-    if pi is not None:
-        pi_arr = np.ascontiguousarray(pi, dtype=np.uint32)
-        n_null = _null_pool_size(names, t_names, nullHypothesis)
-        if pi_arr.ndim != 2 or pi_arr.shape != (int(nPermutations), n_null):
-            raise L.NetRepError(L.NR_ERR_INVALID, f"pi must have shape (nPermutations, n_null) = "
-                                                  f"({int(nPermutations)}, {n_null}), got {pi_arr.shape}")
+    call = _DataPermutationCall(discProps, t_names, moduleAssignments, modules, nPermutations, nCores,
+                                nullHypothesis, verbose, seed, pi)
     tn, _k1 = _strv(t_names)
-    an, _k2 = _strv(names)
-    al, _k3 = _strv(labels)
-    mo, _k4 = _strv(modules)
-    if verbose and not _progress_user_set:
-        _install_progress(_print_progress)
     rc = lib.netrep_PermutationProcedureFromData(
-        C.byref(dp), _dptr(data), int(bool(scaleData)), L.net_type_code(networkType, tom, corType), float(beta), s, n, tn,
-        an,
-        al, len(names), mo, nm_, int(nPermutations), int(nCores), str(nullHypothesis).encode(),
-        int(bool(verbose)), int(seed) & (2**64 - 1),
-        pi_arr.ctypes.data_as(C.POINTER(C.c_uint32)) if pi_arr is not None else None, _dptr(nulls),
-        _dptr(observed))
-    return _permutation_result(rc, modules, True, observed, nulls, nPermutations)
+        C.byref(call.dp), _dptr(data), int(bool(scaleData)), L.net_type_code(networkType, tom, corType),
+        float(beta), s, n, tn, *call.args)
+    return call.result(rc)
 
 
 def BuildNetwork(data, beta: float, networkType: str = "unsigned", scaleData: bool = True, tom: bool = False,
                  corType: str = "pearson"):
     """(correlation, network) of a data matrix, built on the GPU as the from-data
     path builds them (netrep_BuildNetwork) and copied back, for callers who
-    still need host matrices (the discovery-side calls). ``data`` is raw
+    still need host matrices (the discovery-side calls have a from-data route
+    of their own: FromDataDataset, IntermediatePropertiesFromData). ``data`` is raw
     unless ``scaleData=False``. ``tom=True``: the network returned is the
     topological overlap matrix of the adjacency. ``corType`` 'spearman' or
     'bicor': the correlation returned is Spearman's or WGCNA's biweight
@@ -578,47 +617,62 @@ def PermutationProcedureNoData(discProps: dict, tCorr: RMatrix, tNet: RMatrix, m
                         nCores, nullHypothesis, verbose, seed, pi)
 
 
+class _NetPropsCall:
+    """The module arguments and output buffers of a NetProps entry (``args``:
+    from ma_names to k_all_out, in the C order) for a dataset of ``s`` samples
+    (0: no data), and the unpacking of what the call wrote."""
+
+    def __init__(self, module_assignments, modules, s, with_data):
+        self.names, self.labels = _assignments(module_assignments)
+        self.modules = [str(m) for m in modules]
+        self.s, self.with_data = s, with_data
+        k_all = {}
+        for lab in self.labels:
+            k_all[lab] = k_all.get(lab, 0) + 1
+        tot = sum(k_all.get(m, 0) for m in self.modules)
+        nm_ = len(self.modules)
+        self.deg = np.empty(max(tot, 1))
+        self.aw = np.empty(max(nm_, 1))
+        self.kk = np.zeros(max(nm_, 1), dtype=np.int64)
+        self.nc = np.empty(max(tot, 1)) if with_data else None
+        self.sp = np.empty(max(nm_ * s, 1)) if with_data else None
+        self.coh = np.empty(max(nm_, 1)) if with_data else None
+        an, _k2 = _strv(self.names)
+        al, _k3 = _strv(self.labels)
+        mo, _k4 = _strv(self.modules)
+        self._keep = (_k2, _k3, _k4)
+        self.args = (an, al, len(self.names), mo, nm_, _dptr(self.deg), _dptr(self.nc), _dptr(self.sp),
+                     _dptr(self.coh), _dptr(self.aw), self.kk.ctypes.data_as(C.POINTER(C.c_int64)))
+
+    def result(self) -> dict:
+        mod_nodes = {}
+        for nm, lab in zip(self.names, self.labels):
+            mod_nodes.setdefault(lab, []).append(nm)
+        res = {}
+        o = 0
+        s = self.s
+        for i, m in enumerate(self.modules):
+            k = int(self.kk[i])
+            entry = {"degree": self.deg[o:o + k].copy(), "avgWeight": float(self.aw[i]),
+                     "node_names": mod_nodes.get(m, [])}
+            if self.with_data:
+                entry.update(summary=self.sp[i * s:(i + 1) * s].copy(), contribution=self.nc[o:o + k].copy(),
+                             coherence=float(self.coh[i]))
+            res[m] = entry
+            o += k
+        return res
+
+
 def _netprops(data, net, module_assignments, modules):
     lib = L.load()
-    names, labels = _assignments(module_assignments)
-    modules = [str(m) for m in modules]
     node_names = list(net.colnames)
     netv = net.f
     x = data.f if data is not None else None
     s = x.shape[0] if x is not None else 0
-    k_all = {}
-    for lab in labels:
-        k_all[lab] = k_all.get(lab, 0) + 1
-    tot = sum(k_all.get(m, 0) for m in modules)
-    nm_ = len(modules)
-    deg = np.empty(max(tot, 1))
-    aw = np.empty(max(nm_, 1))
-    kk = np.zeros(max(nm_, 1), dtype=np.int64)
-    nc = np.empty(max(tot, 1)) if x is not None else None
-    sp = np.empty(max(nm_ * s, 1)) if x is not None else None
-    coh = np.empty(max(nm_, 1)) if x is not None else None
+    call = _NetPropsCall(module_assignments, modules, s, x is not None)
     nn, _k1 = _strv(node_names)
-    an, _k2 = _strv(names)
-    al, _k3 = _strv(labels)
-    mo, _k4 = _strv(modules)
-    L.check_api(lib.netrep_NetProps(_dptr(x), _dptr(netv), s, len(node_names), nn, an, al, len(names),
-                                    mo, nm_, _dptr(deg), _dptr(nc), _dptr(sp), _dptr(coh), _dptr(aw),
-                                    kk.ctypes.data_as(C.POINTER(C.c_int64))))
-    mod_nodes = {}
-    for nm, lab in zip(names, labels):
-        mod_nodes.setdefault(lab, []).append(nm)
-    res = {}
-    o = 0
-    for i, m in enumerate(modules):
-        k = int(kk[i])
-        entry = {"degree": deg[o:o + k].copy(), "avgWeight": float(aw[i]),
-                 "node_names": mod_nodes.get(m, [])}
-        if x is not None:
-            entry.update(summary=sp[i * s:(i + 1) * s].copy(), contribution=nc[o:o + k].copy(),
-                         coherence=float(coh[i]))
-        res[m] = entry
-        o += k
-    return res
+    L.check_api(lib.netrep_NetProps(_dptr(x), _dptr(netv), s, len(node_names), nn, *call.args))
+    return call.result()
 
 
 def NetProps(data: RMatrix, net: RMatrix, moduleAssignments, modules) -> dict:
@@ -629,3 +683,222 @@ def NetProps(data: RMatrix, net: RMatrix, moduleAssignments, modules) -> dict:
 def NetPropsNoData(net: RMatrix, moduleAssignments, modules) -> dict:
     """NetPropsNoData (src/properties.cpp:190-273)."""
     return _netprops(None, net, moduleAssignments, modules)
+
+
+class FromDataDataset:
+    """A dataset built on the GPU from its data matrix alone and kept there
+    (netrep_DatasetFromData), to be used in every role without another upload
+    or build: the discovery side (``intermediate_properties``), network
+    properties (``net_props``) and the test side (``permutation_procedure``).
+    ``data`` (samples x nodes, its colnames the node names; raw unless
+    ``scaleData=False``) is the only upload; ``beta``, ``networkType``, ``tom``
+    and ``corType`` as in PermutationProcedureFromData. Raises ``NetRepError``
+    (``NR_ERR_NONFINITE``) for a constant column. A context manager;
+    ``close()`` frees the device memory (ReleaseResident does not). After
+    ``close()`` every method raises ``NetRepError`` (``NR_ERR_INVALID``)."""
+
+    def __init__(self, data: RMatrix, beta: float, networkType: str = "unsigned", scaleData: bool = True,
+                 tom: bool = False, corType: str = "pearson", nCores: int = 0):
+        self._h = None
+        lib = L.load()
+        self.node_names, x = _named_data(data, "data")
+        self.n_samples, self.n_nodes = x.shape
+        nn, _k1 = _strv(self.node_names)
+        h = C.c_void_p()
+        L.check_api(lib.netrep_DatasetFromData(_dptr(x), int(bool(scaleData)), L.net_type_code(networkType, tom, corType),
+                                               float(beta), self.n_samples, self.n_nodes, nn, int(nCores),
+                                               C.byref(h)))
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise L.NetRepError(L.NR_ERR_INVALID, "the dataset is closed")
+        return self._h
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h is not None:
+            L.load().netrep_DatasetRelease(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # pragma: no cover - interpreter shutdown
+            pass
+
+    def intermediate_properties(self, tNodeNames, moduleAssignments, modules) -> dict:
+        """IntermediateProperties with this dataset as the discovery dataset."""
+        h = self._handle()
+        call = _IntermediateCall(tNodeNames, moduleAssignments, modules, True)
+        L.check_api(L.load().netrep_DatasetIntermediateProperties(h, *call.args))
+        return call.result()
+
+    def net_props(self, moduleAssignments, modules) -> dict:
+        """NetProps of this dataset's network and (scaled) data."""
+        h = self._handle()
+        call = _NetPropsCall(moduleAssignments, modules, self.n_samples, True)
+        L.check_api(L.load().netrep_DatasetNetProps(h, *call.args))
+        return call.result()
+
+    def permutation_procedure(self, discProps: dict, moduleAssignments, modules, nPermutations: int,
+                              nCores: int = 1, nullHypothesis: str = "overlap", verbose: bool = False,
+                              seed: int = DEFAULT_SEED, pi=None) -> dict:
+        """PermutationProcedureFromData with this dataset as the test dataset;
+        the dataset stays resident and unchanged."""
+        h = self._handle()
+        call = _DataPermutationCall(discProps, self.node_names, moduleAssignments, modules, nPermutations, nCores,
+                                    nullHypothesis, verbose, seed, pi)
+        rc = L.load().netrep_DatasetPermutationProcedure(C.byref(call.dp), h, *call.args)
+        return call.result(rc)
+
+    def matrices(self):
+        """(correlation, network) copied back, as BuildNetwork returns them."""
+        h = self._handle()
+        n = self.n_nodes
+        corr = np.empty((n, n), order="F")
+        net = np.empty((n, n), order="F")
+        L.check_api(L.load().netrep_DatasetMatrices(h, _dptr(corr), _dptr(net)))
+        return RMatrix(corr, self.node_names, self.node_names), RMatrix(net, self.node_names, self.node_names)
+
+
+def IntermediatePropertiesFromData(dData: RMatrix, beta: float, tNodeNames, moduleAssignments, modules,
+                                   networkType: str = "unsigned", scaleData: bool = False, tom: bool = False,
+                                   corType: str = "pearson") -> dict:
+    """IntermediateProperties on a discovery dataset given as its data matrix
+    alone (netrep_IntermediatePropertiesFromData): ``dData`` (scaled already
+    unless ``scaleData``, as IntermediateProperties wants it) is the only
+    upload; correlation and network are built on the GPU and never exist on
+    the host."""
+    d_names, x = _named_data(dData, "dData")
+    s, n = x.shape
+    call = _IntermediateCall(tNodeNames, moduleAssignments, modules, True)
+    dn, _k1 = _strv(d_names)
+    L.check_api(L.load().netrep_IntermediatePropertiesFromData(
+        _dptr(x), int(bool(scaleData)), L.net_type_code(networkType, tom, corType), float(beta), s, n, dn,
+        *call.args))
+    return call.result()
+
+
+def NetPropsFromData(data: RMatrix, beta: float, moduleAssignments, modules, networkType: str = "unsigned",
+                     scaleData: bool = True, tom: bool = False, corType: str = "pearson") -> dict:
+    """NetProps on a dataset given as its data matrix alone
+    (netrep_NetPropsFromData): ``data`` is raw and scaled on the GPU (as
+    NetProps scales) unless ``scaleData=False``; the network is built there."""
+    node_names, x = _named_data(data, "data")
+    s, n = x.shape
+    call = _NetPropsCall(moduleAssignments, modules, s, True)
+    nn, _k1 = _strv(node_names)
+    L.check_api(L.load().netrep_NetPropsFromData(
+        _dptr(x), int(bool(scaleData)), L.net_type_code(networkType, tom, corType), float(beta), s, n, nn,
+        *call.args))
+    return call.result()
+
+
+def _as_name_list(x):
+    return [str(x)] if isinstance(x, (str, bytes)) or not hasattr(x, "__iter__") else [str(v) for v in x]
+
+
+def _per_pair(value, di, ti):
+    """`value`, or value[di][ti] of a nested mapping."""
+    if isinstance(value, Mapping):
+        inner = value.get(di)
+        return inner.get(ti) if isinstance(inner, Mapping) else inner
+    return value
+
+
+def modulePreservationFromData(datasets: Mapping, beta, moduleAssignments: Mapping, modules=None, discovery=None,
+                               test=None, nPerm: int = 10000, nullHypothesis: str = "overlap",
+                               alternative: str = "greater", seed: int = DEFAULT_SEED,
+                               networkType: str = "unsigned", scaleData: bool = True, tom: bool = False,
+                               corType: str = "pearson", pi=None) -> dict:
+    """modulePreservation's loop over (discovery, test) pairs
+    (R/modulePreservation.R:553-620) from data matrices alone: no n x n matrix
+    exists on the host. ``datasets`` {name: RMatrix (samples x nodes, colnames
+    the node names)}; ``beta`` a scalar or {name: beta}; ``moduleAssignments``
+    {discovery name: {node: label}}; ``modules`` None (every label but the
+    background "0", in orderAsNumeric order), a list, or {discovery: list};
+    ``discovery`` a name or names (default: the first dataset); ``test`` a
+    name or names, or {discovery: names} (default: every other dataset).
+    One FromDataDataset per dataset name is built on first use and closed
+    when the call returns or raises. ``pi``: explicit shuffles for every pair,
+    or {discovery: {test: pi}}. Returns ``res[discovery][test]`` with
+    modulePreservation's entries (observed, nulls, p.values, nVarsPresent,
+    propVarsPresent, totalSize, alternative, contingency -- the matrix, its
+    dimnames beside it, None without module assignments for the test dataset)
+    plus ``modules``, the row names; a result combineAnalyses accepts."""
+    from .contingency import contingencyTable, order_as_numeric, total_size
+    from .pvalues import permutationTest
+
+    names = [str(k) for k in datasets]
+    data = {str(k): v for k, v in datasets.items()}
+    assign = {str(k): v for k, v in moduleAssignments.items()}
+    disc_names = [names[0]] if discovery is None else _as_name_list(discovery)
+    pairs = []
+    for di in disc_names:
+        if test is None:
+            tis = [t for t in names if t != di]
+        elif isinstance(test, Mapping):
+            tis = _as_name_list(test[di]) if di in test else []
+        else:
+            tis = _as_name_list(test)
+        for ti in tis:
+            if ti != di:                                 # R/modulePreservation.R:515-524
+                pairs.append((di, ti))
+    for nm in {x for p in pairs for x in p}:
+        if nm not in data:
+            raise L.NetRepError(L.NR_ERR_INVALID, f"no dataset named {nm!r}")
+    for di in disc_names:
+        if di not in assign:
+            raise L.NetRepError(L.NR_ERR_INVALID, f"no moduleAssignments for discovery dataset {di!r}")
+
+    def beta_of(nm):
+        return float(beta[nm]) if isinstance(beta, Mapping) else float(beta)
+
+    def modules_of(di):
+        m = modules.get(di) if isinstance(modules, Mapping) else modules
+        if m is None:
+            _n, labels = _assignments(assign[di])
+            return order_as_numeric([lab for lab in dict.fromkeys(labels) if lab != "0"])
+        return order_as_numeric(_as_name_list(m))
+
+    resident = {}
+
+    def dataset(nm):
+        if nm not in resident:
+            resident[nm] = FromDataDataset(data[nm], beta_of(nm), networkType=networkType, scaleData=scaleData,
+                                           tom=tom, corType=corType)
+        return resident[nm]
+
+    res = {}
+    try:
+        for di, ti in pairs:
+            mods = modules_of(di)
+            t_names = [str(n) for n in data[ti].colnames]
+            ct = contingencyTable([assign[di], assign.get(ti)], mods, t_names)
+            disc_props = dataset(di).intermediate_properties(t_names, assign[di], mods)
+            perms = dataset(ti).permutation_procedure(disc_props, assign[di], mods, nPerm,
+                                                      nullHypothesis=nullHypothesis, seed=seed,
+                                                      pi=_per_pair(pi, di, ti))
+            out = {"observed": perms["observed"], "nVarsPresent": ct["varsPres"],
+                   "propVarsPresent": ct["propVarsPres"], "alternative": alternative, "modules": mods,
+                   "contingency": None}                     # without the test dataset's assignments
+            if ct["contingency"] is not None:
+                out["contingency"], rows, cols = ct["contingency"]
+                out["contingency_dimnames"] = (rows, cols)
+            if nPerm > 0:
+                out["nulls"] = perms["nulls"]
+                out["totalSize"] = total_size(nullHypothesis, ct["overlapVars"], len(t_names))
+                out["p.values"] = permutationTest(out["nulls"], out["observed"], ct["varsPres"], out["totalSize"],
+                                                  alternative, modules=mods)
+            res.setdefault(di, {})[ti] = out
+    finally:
+        for d in resident.values():
+            d.close()
+    return res

@@ -138,10 +138,14 @@ void give_ctx(CtxPtr& c) {
   g_pool.push_back({it->second, std::move(c)});
 }
 
-// Returns every context of a call to the pool when it goes out of scope.
+// Returns every context of a call to the pool when it goes out of scope;
+// with `keep`, the first one (the primary, which holds a dataset handle's
+// dataset) goes back to its owner as it is instead.
 struct CtxLease {
   std::vector<CtxPtr>* v;
+  CtxPtr* keep = nullptr;
   ~CtxLease() {
+    if (keep && !v->empty() && (*v)[0]) *keep = std::move((*v)[0]);
     for (CtxPtr& c : *v) give_ctx(c);
   }
 };
@@ -469,14 +473,24 @@ int netrep_PrefetchTestDataset(const double* t_data, const double* t_corr, const
 namespace {
 
 // PermutationProcedure with the dataset given either as host matrices or as a
-// context that already holds it (`preloaded`: a prefetch or a file load).
+// context that already holds it (`preloaded`: a prefetch, a file load or a
+// dataset handle's). With `keep`, the preloaded context is handed back there
+// on every return, its dataset still resident, instead of going to the pool.
 int permutation_impl(const netrep_disc_props* disc, bool with_data, const double* t_data,
                      const double* t_corr, const double* t_net, int64_t n_samples, int64_t n_nodes,
                      const char* const* t_names, const char* const* ma_names, const char* const* ma_labels,
                      int64_t n_assign, const char* const* modules, int64_t n_modules, int64_t n_perm,
                      const char* null_hypothesis, int32_t verbose, uint64_t seed, const uint32_t* pi,
                      double* nulls_out, double* observed_out, CtxPtr preloaded, int32_t n_cores,
-                     int64_t pi_len = -1) {
+                     int64_t pi_len = -1, CtxPtr* keep = nullptr) {
+  // returns before the lease below exists
+  struct HandBack {
+    CtxPtr* keep;
+    CtxPtr* from;
+    ~HandBack() {
+      if (keep && *from) *keep = std::move(*from);
+    }
+  } hand_back{keep, &preloaded};
   if (with_data && !disc->contribution)
     return set_err(NR_ERR_INVALID, "discProps has no 'contribution' but tData was given");
   const std::string null_type = null_hypothesis ? null_hypothesis : "overlap";
@@ -549,7 +563,7 @@ int permutation_impl(const netrep_disc_props* disc, bool with_data, const double
   int n_dev = 1;
   const int n_gpu = (n_perm > 0) ? (int)std::min<int64_t>(gpu_count_requested(&n_dev), std::max<int64_t>(n_perm, 1)) : 1;
   std::vector<CtxPtr> ctxs(n_gpu);
-  CtxLease lease{&ctxs};  // the contexts go back to the pool (without the dataset) on every return
+  CtxLease lease{&ctxs, keep};  // the contexts go back to the pool (without the dataset) on every return
   // a dataset already resident (prefetched or loaded from files) becomes GPU 0's
   ctxs[0] = std::move(preloaded);
   const bool prefetched = ctxs[0] != nullptr;
@@ -793,6 +807,202 @@ int from_data_once(const netrep_disc_props* disc, const double* t_data, int32_t 
                           observed_out, std::move(ctx), n_cores);
 }
 
+// IntermediateProperties' module resolution (src/discProps.cpp:64-79): the
+// modules with a node in the test node list, their nodes as discovery indices.
+struct DiscSets {
+  std::vector<int64_t> node_off{0};
+  std::vector<int32_t> idx;
+  std::vector<int64_t> which;  // row in `modules` of each set
+};
+
+int resolve_disc_sets(const NameMap& d_idx_map, const char* const* t_node_names, int64_t n_t_nodes,
+                      const char* const* ma_names, const char* const* ma_labels, int64_t n_assign,
+                      const char* const* modules, int64_t n_modules, int64_t* degree_len, int64_t* corr_len,
+                      int64_t* contribution_len, DiscSets& ds) {
+  const NameMap t_idx_map = make_idx_map(t_node_names, n_t_nodes);
+  const ModMap present = make_mod_map(ma_names, ma_labels, n_assign, &t_idx_map);
+  for (int64_t mi = 0; mi < n_modules; ++mi) {
+    degree_len[mi] = corr_len[mi] = 0;
+    if (contribution_len) contribution_len[mi] = 0;
+    const std::vector<std::string>* nodes = present.find(modules[mi]);
+    if (!nodes || nodes->empty()) continue;
+    for (const std::string& nm : *nodes) {
+      auto it = d_idx_map.find(nm);  // GetNodeIdx (src/utils.cpp:157) throws on a miss
+      if (it == d_idx_map.end())
+        return set_err(NR_ERR_INVALID, "node '" + nm + "' of moduleAssignments is not in the discovery dataset");
+      ds.idx.push_back((int32_t)it->second);
+    }
+    ds.node_off.push_back((int64_t)ds.idx.size());
+    ds.which.push_back(mi);
+  }
+  return NR_OK;
+}
+
+// The discovery vectors of the resolved modules from the context's resident
+// dataset, concatenated in `modules` order (src/discProps.cpp:119-125).
+int disc_vectors(nr_ctx* ctx, const DiscSets& ds, bool with_data, double* degree_out, int64_t* degree_len,
+                 double* corr_out, int64_t* corr_len, double* contribution_out, int64_t* contribution_len) {
+  const int32_t n_mod = (int32_t)ds.which.size();
+  const std::vector<int64_t>& node_off = ds.node_off;
+  const int64_t nodes = node_off.back();
+  int64_t n_cv = 0;
+  for (int32_t m = 0; m < n_mod; ++m) {
+    const int64_t k = node_off[m + 1] - node_off[m];
+    n_cv += k * (k - 1) / 2;
+  }
+  std::vector<double> cv((size_t)std::max<int64_t>(n_cv, 1)), wd((size_t)nodes), nc(with_data ? (size_t)nodes : 0);
+  const int rc = nr_module_vectors(ctx, n_mod, node_off.data(), ds.idx.data(), cv.data(), wd.data(), nullptr,
+                                   with_data ? nc.data() : nullptr, nullptr, nullptr);
+  if (rc) return ctx_err(rc, ctx);
+  int64_t o_cv = 0, o_n = 0;
+  for (int32_t m = 0; m < n_mod; ++m) {
+    const int64_t mi = ds.which[m];
+    const int64_t k = node_off[m + 1] - node_off[m];
+    const int64_t kc = k * (k - 1) / 2;
+    std::memcpy(corr_out + o_cv, cv.data() + o_cv, (size_t)kc * sizeof(double));
+    std::memcpy(degree_out + o_n, wd.data() + node_off[m], (size_t)k * sizeof(double));
+    if (with_data) std::memcpy(contribution_out + o_n, nc.data() + node_off[m], (size_t)k * sizeof(double));
+    corr_len[mi] = kc;
+    degree_len[mi] = k;
+    if (with_data) contribution_len[mi] = k;
+    o_cv += kc;
+    o_n += k;
+  }
+  return NR_OK;
+}
+
+double na_real() {
+  const uint64_t b = 0x7FF00000000007A2ull;
+  double d;
+  std::memcpy(&d, &b, 8);
+  return d;
+}
+
+// NetProps' module resolution: per module all its nodes (k_all), and the
+// present ones as dataset index + slot in the module's output.
+struct PropSets {
+  std::vector<int64_t> node_off{0}, out_off;
+  std::vector<int32_t> idx, slot;
+  std::vector<int64_t> which;
+};
+
+// Resolves the modules and NA-initialises the outputs (src/properties.cpp:131-139).
+void resolve_prop_sets(const NameMap& node_idx, const char* const* ma_names, const char* const* ma_labels,
+                       int64_t n_assign, const char* const* modules, int64_t n_modules, bool with_data,
+                       int64_t n_samples, double* degree_out, double* contribution_out, double* summary_out,
+                       double* coherence_out, double* avg_weight_out, int64_t* k_all_out, PropSets& ps) {
+  const double na = na_real();
+  const ModMap all = make_mod_map(ma_names, ma_labels, n_assign, nullptr);  // src/properties.cpp:108
+  std::vector<int64_t> k_all(n_modules, 0);
+  std::vector<int64_t>& out_off = ps.out_off;
+  out_off.assign(n_modules + 1, 0);
+  for (int64_t mi = 0; mi < n_modules; ++mi) {
+    const std::vector<std::string>* nodes = all.find(modules[mi]);
+    k_all[mi] = nodes ? (int64_t)nodes->size() : 0;
+    out_off[mi + 1] = out_off[mi] + k_all[mi];
+    if (!nodes) continue;
+    const size_t before = ps.idx.size();
+    for (size_t j = 0; j < nodes->size(); ++j) {
+      auto it = node_idx.find((*nodes)[j]);
+      if (it == node_idx.end()) continue;
+      ps.idx.push_back((int32_t)it->second);
+      ps.slot.push_back((int32_t)j);
+    }
+    if (ps.idx.size() > before) {
+      ps.node_off.push_back((int64_t)ps.idx.size());
+      ps.which.push_back(mi);
+    }
+  }
+  for (int64_t mi = 0; mi < n_modules; ++mi) {
+    k_all_out[mi] = k_all[mi];
+    avg_weight_out[mi] = na;
+    for (int64_t j = out_off[mi]; j < out_off[mi + 1]; ++j) {
+      degree_out[j] = na;
+      if (with_data) contribution_out[j] = na;
+    }
+    if (with_data) {
+      coherence_out[mi] = na;
+      for (int64_t s = 0; s < n_samples; ++s) summary_out[mi * n_samples + s] = na;
+    }
+  }
+}
+
+// The network properties of the resolved modules from the context's resident
+// dataset, filled into the outputs' slots.
+int prop_vectors(nr_ctx* ctx, const PropSets& ps, bool with_data, int64_t n_samples, double* degree_out,
+                 double* contribution_out, double* summary_out, double* coherence_out, double* avg_weight_out) {
+  const double na = na_real();
+  const int32_t n_mod = (int32_t)ps.which.size();
+  const std::vector<int64_t>& node_off = ps.node_off;
+  const int64_t nodes = node_off.back();
+  std::vector<double> wd((size_t)nodes), aw((size_t)n_mod), nc, sp, coh;
+  if (with_data) {
+    nc.resize((size_t)nodes);
+    sp.resize((size_t)(n_mod * n_samples));
+    coh.resize((size_t)n_mod);
+  }
+  const int rc = nr_module_vectors(ctx, n_mod, node_off.data(), ps.idx.data(), nullptr, wd.data(), aw.data(),
+                                   with_data ? nc.data() : nullptr, with_data ? sp.data() : nullptr,
+                                   with_data ? coh.data() : nullptr);
+  if (rc) return ctx_err(rc, ctx);
+  auto na_if = [&](double x) { return std::isfinite(x) ? x : na; };
+  for (int32_t m = 0; m < n_mod; ++m) {
+    const int64_t mi = ps.which[m];
+    avg_weight_out[mi] = aw[m];  // AverageEdgeWeight result kept as is (src/properties.cpp:160)
+    for (int64_t c = node_off[m]; c < node_off[m + 1]; ++c) {
+      const int64_t j = ps.out_off[mi] + ps.slot[c];  // Fill (src/utils.cpp:245-257)
+      degree_out[j] = wd[c];
+      if (with_data) contribution_out[j] = na_if(nc[c]);  // :176
+    }
+    if (with_data) {
+      coherence_out[mi] = na_if(coh[m]);  // :177-179
+      for (int64_t s = 0; s < n_samples; ++s)
+        summary_out[mi * n_samples + s] = na_if(sp[m * n_samples + s]);  // :175
+    }
+  }
+  return NR_OK;
+}
+
+}  // namespace
+
+// The opaque handle of include/netrep_gpu.h: a context that holds a from-data
+// dataset, and the node names it was built with.
+struct netrep_dataset {
+  std::mutex mu;
+  CtxPtr ctx;
+  std::vector<std::string> names;
+  std::vector<const char*> name_ptrs;
+  NameMap idx_map;
+  int64_t n_nodes = 0, n_samples = 0;
+  int32_t n_cores = 0;
+  ~netrep_dataset() { give_ctx(ctx); }
+};
+
+namespace {
+
+int dataset_from_data_once(const double* data, int32_t scale_data, int32_t net_type, double beta, int64_t n_samples,
+                           int64_t n_nodes, int32_t n_cores, CtxPtr& ctx) {
+  int rc = open_from_data(data, scale_data, net_type, beta, n_samples, n_nodes, n_cores, ctx);
+  if (rc) return rc;
+  int cf = 0, nf = 0;
+  nr_dataset_finite(ctx.get(), &cf, &nf);
+  if (!cf || !nf) {
+    give_ctx(ctx);
+    return set_err(NR_ERR_NONFINITE, "matrices cannot have non-finite or missing values");
+  }
+  return NR_OK;
+}
+
+int no_dataset(const char* entry) {
+  return set_err(NR_ERR_INVALID, std::string("invalid arguments to ") + entry + " (no dataset)");
+}
+
+// With the handle's mutex held: its context is there.
+int live(netrep_dataset* d) {
+  if (!d->ctx) return set_err(NR_ERR_INVALID, "the dataset's context was lost to an earlier error");
+  return NR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -945,29 +1155,12 @@ int netrep_IntermediateProperties(const double* d_data, const double* d_corr, co
   const bool with_data = d_data != nullptr;
   if (with_data && (!contribution_out || !contribution_len))
     return set_err(NR_ERR_INVALID, "contribution buffers required with data");
-  // src/discProps.cpp:64-79
-  const NameMap d_idx_map = make_idx_map(d_names, n_nodes);
-  const NameMap t_idx_map = make_idx_map(t_node_names, n_t_nodes);
-  const ModMap present = make_mod_map(ma_names, ma_labels, n_assign, &t_idx_map);
-  std::vector<int64_t> node_off{0};
-  std::vector<int32_t> idx;
-  std::vector<int64_t> which;
-  for (int64_t mi = 0; mi < n_modules; ++mi) {
-    degree_len[mi] = corr_len[mi] = 0;
-    if (with_data) contribution_len[mi] = 0;
-    const std::vector<std::string>* nodes = present.find(modules[mi]);
-    if (!nodes || nodes->empty()) continue;
-    for (const std::string& nm : *nodes) {
-      auto it = d_idx_map.find(nm);  // GetNodeIdx (src/utils.cpp:157) throws on a miss
-      if (it == d_idx_map.end())
-        return set_err(NR_ERR_INVALID, "node '" + nm + "' of moduleAssignments is not in the discovery dataset");
-      idx.push_back((int32_t)it->second);
-    }
-    node_off.push_back((int64_t)idx.size());
-    which.push_back(mi);
-  }
-  const int32_t n_mod = (int32_t)which.size();
-  if (n_mod == 0) return NR_OK;
+  DiscSets sets;
+  if (int rc = resolve_disc_sets(make_idx_map(d_names, n_nodes), t_node_names, n_t_nodes, ma_names, ma_labels,
+                                 n_assign, modules, n_modules, degree_len, corr_len,
+                                 with_data ? contribution_len : nullptr, sets))
+    return rc;
+  if (sets.which.empty()) return NR_OK;
   // The discovery dataset stays resident across the calls of one discovery
   // dataset's loop over test datasets (the reference loads it once per di,
   // R/modulePreservation.R:553-590): uploaded only when these arrays are not
@@ -982,33 +1175,8 @@ int netrep_IntermediateProperties(const double* d_data, const double* d_corr, co
     if (rc) return ctx_err(rc, ctx.get());
     g_disc_res.keep(std::move(ctx), d_data, d_corr, d_net, n_samples, n_nodes);
   }
-  nr_ctx* const ctx = g_disc_res.ctx.get();
-  const int64_t nodes = node_off.back();
-  int64_t n_cv = 0;
-  for (int32_t m = 0; m < n_mod; ++m) {
-    const int64_t k = node_off[m + 1] - node_off[m];
-    n_cv += k * (k - 1) / 2;
-  }
-  std::vector<double> cv((size_t)std::max<int64_t>(n_cv, 1)), wd((size_t)nodes), nc(with_data ? (size_t)nodes : 0);
-  rc = nr_module_vectors(ctx, n_mod, node_off.data(), idx.data(), cv.data(), wd.data(), nullptr,
-                         with_data ? nc.data() : nullptr, nullptr, nullptr);
-  if (rc) return ctx_err(rc, ctx);
-  // Concatenate in `modules` order (src/discProps.cpp:119-125).
-  int64_t o_cv = 0, o_n = 0;
-  for (int32_t m = 0; m < n_mod; ++m) {
-    const int64_t mi = which[m];
-    const int64_t k = node_off[m + 1] - node_off[m];
-    const int64_t kc = k * (k - 1) / 2;
-    std::memcpy(corr_out + o_cv, cv.data() + o_cv, (size_t)kc * sizeof(double));
-    std::memcpy(degree_out + o_n, wd.data() + node_off[m], (size_t)k * sizeof(double));
-    if (with_data) std::memcpy(contribution_out + o_n, nc.data() + node_off[m], (size_t)k * sizeof(double));
-    corr_len[mi] = kc;
-    degree_len[mi] = k;
-    if (with_data) contribution_len[mi] = k;
-    o_cv += kc;
-    o_n += k;
-  }
-  return NR_OK;
+  return disc_vectors(g_disc_res.ctx.get(), sets, with_data, degree_out, degree_len, corr_out, corr_len,
+                      contribution_out, contribution_len);
 } catch (const std::bad_alloc&) {
   return set_err(NR_ERR_OOM, "host memory allocation failed");
 } catch (const std::exception& e) {
@@ -1027,46 +1195,11 @@ int netrep_NetProps(const double* data, const double* net, int64_t n_samples, in
   const bool with_data = data != nullptr;
   if (with_data && (!contribution_out || !summary_out || !coherence_out))
     return set_err(NR_ERR_INVALID, "contribution/summary/coherence buffers required with data");
-  const double na = [] { uint64_t b = 0x7FF00000000007A2ull; double d; std::memcpy(&d, &b, 8); return d; }();
-  const NameMap node_idx = make_idx_map(node_names, n_nodes);
-  const ModMap all = make_mod_map(ma_names, ma_labels, n_assign, nullptr);  // src/properties.cpp:108
-
-  // Per module: all nodes (k_all), present nodes -> dataset index + slot.
-  std::vector<int64_t> node_off{0}, k_all(n_modules, 0), out_off(n_modules + 1, 0);
-  std::vector<int32_t> idx, slot;
-  std::vector<int64_t> which;
-  for (int64_t mi = 0; mi < n_modules; ++mi) {
-    const std::vector<std::string>* nodes = all.find(modules[mi]);
-    k_all[mi] = nodes ? (int64_t)nodes->size() : 0;
-    out_off[mi + 1] = out_off[mi] + k_all[mi];
-    if (!nodes) continue;
-    const size_t before = idx.size();
-    for (size_t j = 0; j < nodes->size(); ++j) {
-      auto it = node_idx.find((*nodes)[j]);
-      if (it == node_idx.end()) continue;
-      idx.push_back((int32_t)it->second);
-      slot.push_back((int32_t)j);
-    }
-    if (idx.size() > before) {
-      node_off.push_back((int64_t)idx.size());
-      which.push_back(mi);
-    }
-  }
-  // NA-initialised outputs (src/properties.cpp:131-139).
-  for (int64_t mi = 0; mi < n_modules; ++mi) {
-    k_all_out[mi] = k_all[mi];
-    avg_weight_out[mi] = na;
-    for (int64_t j = out_off[mi]; j < out_off[mi + 1]; ++j) {
-      degree_out[j] = na;
-      if (with_data) contribution_out[j] = na;
-    }
-    if (with_data) {
-      coherence_out[mi] = na;
-      for (int64_t s = 0; s < n_samples; ++s) summary_out[mi * n_samples + s] = na;
-    }
-  }
-  const int32_t n_mod = (int32_t)which.size();
-  if (n_mod == 0) return NR_OK;
+  PropSets sets;
+  resolve_prop_sets(make_idx_map(node_names, n_nodes), ma_names, ma_labels, n_assign, modules, n_modules, with_data,
+                    n_samples, degree_out, contribution_out, summary_out, coherence_out, avg_weight_out, k_all_out,
+                    sets);
+  if (sets.which.empty()) return NR_OK;
   // NetProps scales internally (src/properties.cpp:49): the raw data is
   // scaled on the device on its way into HBM. No correlation matrix on this
   // path: the network doubles as the (unused) correlation operand and
@@ -1083,34 +1216,8 @@ int netrep_NetProps(const double* data, const double* net, int64_t n_samples, in
     if (rc) return ctx_err(rc, ctx.get());
     g_props_res.keep(std::move(ctx), data, net, net, n_samples, n_nodes);
   }
-  nr_ctx* const ctx = g_props_res.ctx.get();
-  const int64_t nodes = node_off.back();
-  std::vector<double> wd((size_t)nodes), aw((size_t)n_mod), nc, sp, coh;
-  if (with_data) {
-    nc.resize((size_t)nodes);
-    sp.resize((size_t)(n_mod * n_samples));
-    coh.resize((size_t)n_mod);
-  }
-  rc = nr_module_vectors(ctx, n_mod, node_off.data(), idx.data(), nullptr, wd.data(), aw.data(),
-                         with_data ? nc.data() : nullptr, with_data ? sp.data() : nullptr,
-                         with_data ? coh.data() : nullptr);
-  if (rc) return ctx_err(rc, ctx);
-  auto na_if = [&](double x) { return std::isfinite(x) ? x : na; };
-  for (int32_t m = 0; m < n_mod; ++m) {
-    const int64_t mi = which[m];
-    avg_weight_out[mi] = aw[m];  // AverageEdgeWeight result kept as is (src/properties.cpp:160)
-    for (int64_t c = node_off[m]; c < node_off[m + 1]; ++c) {
-      const int64_t j = out_off[mi] + slot[c];  // Fill (src/utils.cpp:245-257)
-      degree_out[j] = wd[c];
-      if (with_data) contribution_out[j] = na_if(nc[c]);  // :176
-    }
-    if (with_data) {
-      coherence_out[mi] = na_if(coh[m]);  // :177-179
-      for (int64_t s = 0; s < n_samples; ++s)
-        summary_out[mi * n_samples + s] = na_if(sp[m * n_samples + s]);  // :175
-    }
-  }
-  return NR_OK;
+  return prop_vectors(g_props_res.ctx.get(), sets, with_data, n_samples, degree_out, contribution_out, summary_out,
+                      coherence_out, avg_weight_out);
 } catch (const std::bad_alloc&) {
   return set_err(NR_ERR_OOM, "host memory allocation failed");
 } catch (const std::exception& e) {
@@ -1148,6 +1255,181 @@ int netrep_CheckFinite(const double* mat, int64_t nrow, int64_t ncol) try {
   return set_err(NR_ERR_OOM, "host memory allocation failed");
 } catch (const std::exception& e) {
   return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetFromData(const double* data, int32_t scale_data, int32_t net_type, double beta, int64_t n_samples,
+                           int64_t n_nodes, const char* const* node_names, int32_t n_cores,
+                           netrep_dataset** out) try {
+  if (out) *out = nullptr;
+  if (int rc = check_from_data_args(data, net_type, beta, n_samples, n_nodes)) return rc;
+  if (!node_names || !out) return set_err(NR_ERR_INVALID, "invalid arguments to DatasetFromData");
+  std::unique_ptr<netrep_dataset> d(new netrep_dataset());
+  d->names.reserve((size_t)n_nodes);
+  for (int64_t i = 0; i < n_nodes; ++i) {
+    if (!node_names[i]) return set_err(NR_ERR_INVALID, "invalid arguments to DatasetFromData (a NULL node name)");
+    d->names.emplace_back(node_names[i]);
+  }
+  for (const std::string& s : d->names) d->name_ptrs.push_back(s.c_str());
+  d->idx_map = make_idx_map(d->name_ptrs.data(), n_nodes);
+  d->n_nodes = n_nodes;
+  d->n_samples = n_samples;
+  d->n_cores = n_cores;
+  int rc = dataset_from_data_once(data, scale_data, net_type, beta, n_samples, n_nodes, n_cores, d->ctx);
+  if (rc == NR_ERR_OOM) {  // as netrep_PermutationProcedureFromData: free what is held between calls, once
+    netrep_ReleaseResident();
+    rc = dataset_from_data_once(data, scale_data, net_type, beta, n_samples, n_nodes, n_cores, d->ctx);
+  }
+  if (rc) return rc;
+  *out = d.release();
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+void netrep_DatasetRelease(netrep_dataset* d) {
+  if (!d) return;
+  { std::lock_guard<std::mutex> lk(d->mu); }  // a call in flight on another thread finishes first
+  delete d;
+}
+
+int netrep_DatasetShape(netrep_dataset* d, int64_t* n_nodes, int64_t* n_samples) {
+  if (!d) return set_err(NR_ERR_INVALID, "invalid arguments to DatasetShape (no dataset)");
+  if (n_nodes) *n_nodes = d->n_nodes;
+  if (n_samples) *n_samples = d->n_samples;
+  return NR_OK;
+}
+
+int netrep_DatasetMatrices(netrep_dataset* d, double* corr_out, double* net_out) try {
+  if (!d) return no_dataset("DatasetMatrices");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  const int rc = nr_get_dataset_matrices(d->ctx.get(), corr_out, net_out);
+  return rc ? ctx_err(rc, d->ctx.get()) : NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetIntermediateProperties(netrep_dataset* d, const char* const* t_node_names, int64_t n_t_nodes,
+                                         const char* const* ma_names, const char* const* ma_labels,
+                                         int64_t n_assign, const char* const* modules, int64_t n_modules,
+                                         double* degree_out, int64_t* degree_len, double* corr_out,
+                                         int64_t* corr_len, double* contribution_out,
+                                         int64_t* contribution_len) try {
+  if (!d) return no_dataset("DatasetIntermediateProperties");
+  if (!t_node_names || !ma_names || !ma_labels || !modules || !degree_out || !degree_len || !corr_out ||
+      !corr_len || !contribution_out || !contribution_len)
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetIntermediateProperties");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  DiscSets sets;
+  if (int rc = resolve_disc_sets(d->idx_map, t_node_names, n_t_nodes, ma_names, ma_labels, n_assign, modules,
+                                 n_modules, degree_len, corr_len, contribution_len, sets))
+    return rc;
+  if (sets.which.empty()) return NR_OK;
+  return disc_vectors(d->ctx.get(), sets, true, degree_out, degree_len, corr_out, corr_len, contribution_out,
+                      contribution_len);
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetNetProps(netrep_dataset* d, const char* const* ma_names, const char* const* ma_labels,
+                           int64_t n_assign, const char* const* modules, int64_t n_modules, double* degree_out,
+                           double* contribution_out, double* summary_out, double* coherence_out,
+                           double* avg_weight_out, int64_t* k_all_out) try {
+  if (!d) return no_dataset("DatasetNetProps");
+  if (!ma_names || !ma_labels || !modules || !degree_out || !contribution_out || !summary_out || !coherence_out ||
+      !avg_weight_out || !k_all_out)
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetNetProps");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  PropSets sets;
+  resolve_prop_sets(d->idx_map, ma_names, ma_labels, n_assign, modules, n_modules, true, d->n_samples, degree_out,
+                    contribution_out, summary_out, coherence_out, avg_weight_out, k_all_out, sets);
+  if (sets.which.empty()) return NR_OK;
+  return prop_vectors(d->ctx.get(), sets, true, d->n_samples, degree_out, contribution_out, summary_out,
+                      coherence_out, avg_weight_out);
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetPermutationProcedure(const netrep_disc_props* disc, netrep_dataset* d,
+                                       const char* const* ma_names, const char* const* ma_labels, int64_t n_assign,
+                                       const char* const* modules, int64_t n_modules, int64_t n_perm,
+                                       int32_t n_cores, const char* null_hypothesis, int32_t verbose, uint64_t seed,
+                                       const uint32_t* pi, double* nulls_out, double* observed_out) try {
+  if (!d) return no_dataset("DatasetPermutationProcedure");
+  if (!disc || !ma_names || !ma_labels || !modules || !observed_out || n_perm < 0 || (n_perm > 0 && !nulls_out))
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetPermutationProcedure");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  // the handle's context is the run's primary one and comes back on every return
+  const int rc = permutation_impl(disc, true, nullptr, nullptr, nullptr, d->n_samples, d->n_nodes,
+                                  d->name_ptrs.data(), ma_names, ma_labels, n_assign, modules, n_modules, n_perm,
+                                  null_hypothesis, verbose, seed, pi, nulls_out, observed_out, std::move(d->ctx),
+                                  n_cores, -1, &d->ctx);
+  if (nr_ctx* c = d->ctx.get()) {
+    if (rc == NR_ERR_CANCELLED) {
+      // a cancellation that reached the context after its run had returned is
+      // consumed by an empty run, so the next call on the handle starts clean
+      double none = 0.0;
+      (void)nr_run(c, 0, 0, seed, nullptr, &none);
+    }
+    // between calls the handle holds its dataset only, as a pooled context holds nothing
+    (void)nr_release_scratch(c);
+    (void)nr_ctx_set_host_threads(c, d->n_cores != 0 ? d->n_cores : nr_get_host_threads());
+  }
+  return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_IntermediatePropertiesFromData(const double* d_data, int32_t scale_data, int32_t net_type, double beta,
+                                          int64_t n_samples, int64_t n_nodes, const char* const* d_names,
+                                          const char* const* t_node_names, int64_t n_t_nodes,
+                                          const char* const* ma_names, const char* const* ma_labels,
+                                          int64_t n_assign, const char* const* modules, int64_t n_modules,
+                                          double* degree_out, int64_t* degree_len, double* corr_out,
+                                          int64_t* corr_len, double* contribution_out, int64_t* contribution_len) {
+  if (int rc = check_from_data_args(d_data, net_type, beta, n_samples, n_nodes)) return rc;
+  if (!d_names || !t_node_names || !ma_names || !ma_labels || !modules || !degree_out || !degree_len || !corr_out ||
+      !corr_len || !contribution_out || !contribution_len)
+    return set_err(NR_ERR_INVALID, "invalid arguments to IntermediatePropertiesFromData");
+  netrep_dataset* d = nullptr;
+  int rc = netrep_DatasetFromData(d_data, scale_data, net_type, beta, n_samples, n_nodes, d_names, 0, &d);
+  if (rc) return rc;
+  rc = netrep_DatasetIntermediateProperties(d, t_node_names, n_t_nodes, ma_names, ma_labels, n_assign, modules,
+                                            n_modules, degree_out, degree_len, corr_out, corr_len, contribution_out,
+                                            contribution_len);
+  netrep_DatasetRelease(d);
+  return rc;
+}
+
+int netrep_NetPropsFromData(const double* data, int32_t scale_data, int32_t net_type, double beta, int64_t n_samples,
+                            int64_t n_nodes, const char* const* node_names, const char* const* ma_names,
+                            const char* const* ma_labels, int64_t n_assign, const char* const* modules,
+                            int64_t n_modules, double* degree_out, double* contribution_out, double* summary_out,
+                            double* coherence_out, double* avg_weight_out, int64_t* k_all_out) {
+  if (int rc = check_from_data_args(data, net_type, beta, n_samples, n_nodes)) return rc;
+  if (!node_names || !ma_names || !ma_labels || !modules || !degree_out || !contribution_out || !summary_out ||
+      !coherence_out || !avg_weight_out || !k_all_out)
+    return set_err(NR_ERR_INVALID, "invalid arguments to NetPropsFromData");
+  netrep_dataset* d = nullptr;
+  int rc = netrep_DatasetFromData(data, scale_data, net_type, beta, n_samples, n_nodes, node_names, 0, &d);
+  if (rc) return rc;
+  rc = netrep_DatasetNetProps(d, ma_names, ma_labels, n_assign, modules, n_modules, degree_out, contribution_out,
+                              summary_out, coherence_out, avg_weight_out, k_all_out);
+  netrep_DatasetRelease(d);
+  return rc;
 }
 
 }  // extern "C"
