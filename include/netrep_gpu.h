@@ -36,6 +36,7 @@ extern "C" {
                                  the LDS vectors keep their vectors in device scratch */
 #define NR_ERR_CANCELLED 5    /* nr_cancel() was called during a run */
 #define NR_ERR_NONFINITE 6    /* CheckFinite failure (src/checkFinite.cpp:25-27) */
+#define NR_ERR_INTERNAL 7     /* a kernel's termination guard stopped it (nr_hclust_average) */
 
 #define NR_HOST 0
 #define NR_DEVICE 1
@@ -210,6 +211,66 @@ int nr_sft_finite(nr_ctx* ctx, int* finite);
  * empty); 0 restores the default. It regroups the sums, so k moves at
  * rounding level. */
 int nr_set_sft_row_groups(nr_ctx* ctx, int row_groups);
+
+/* The average-linkage (UPGMA) dendrogram of the resident dataset's nodes, on
+ * the GPU: what R's hclust(as.dist(1 - net), "average") computes, with every
+ * tie broken by rule so that the output is a function of the resident net
+ * alone.
+ * Dissimilarity: d_ij = 1 - net_ij for i != j (net: the adjacency, or the TOM
+ * of a dataset built with NR_NET_TOM), +inf on the diagonal. net must be
+ * symmetric and finite, as every from-data dataset is by construction.
+ * Linkage, by the Lance-Williams update with cluster sizes s as doubles:
+ *   d(k, a u b) = (s_a d(k, a) + s_b d(k, b)) / (s_a + s_b)
+ * as two multiplications, one addition, one division and the size sum, each
+ * rounded to fp64 on its own (never fused).
+ * Algorithm: the nearest-neighbour chain over n slots, one per node at first.
+ *   - The merged cluster lives in the slot of the higher index hi = max(a, b);
+ *     slot lo is retired.
+ *   - An empty chain starts at the lowest-index live slot.
+ *   - The nearest neighbour of the chain's top a is the live slot k != a with
+ *     the smallest d(a, k); ties go to the lowest index, except that the
+ *     chain's previous element is chosen whenever it attains the minimum.
+ *   - When the nearest neighbour is the previous element the two are merged
+ *     at height d(a, b); both are popped and the rest of the chain is kept.
+ *   - Merges are emitted in discovery order: step t = 0 .. n - 2 gives
+ *     id_lo[t], id_hi[t] (the ids of the clusters in slots lo and hi: 0 ..
+ *     n - 1 are nodes, n + u is the cluster of step u), height[t] and size[t]
+ *     (the merged cluster's node count). Heights need not be sorted.
+ * n = 1 writes nothing; n = 2 gives one merge.
+ * Device scratch for the call: the working matrix, 8 n ld bytes (ld = n
+ * rounded up to even; 3.2 GB at n = 20,000), and 64 + 40 n bytes of chain
+ * state; freed before the call returns on every path; a failed allocation
+ * returns NR_ERR_OOM naming the bytes. The resident dataset is read once (in
+ * either pair layout) to fill the working matrix and never written; modules,
+ * null pool and per-batch buffers are not touched.
+ * One workgroup runs the chain in launches of at most M merges each
+ * (nr_set_hclust_merges_per_launch); nr_cancel, from any thread before or
+ * during the call, is honoured between launches and consumed
+ * (NR_ERR_CANCELLED, nothing written). The result does not depend on M.
+ * Termination guard: the kernel counts its nearest-neighbour searches; it
+ * stops, and is not launched again, when the call's total would exceed
+ * 4 n + 16 (the rules need fewer than 3 n) or when a search finds no finite
+ * neighbour while more than one slot is live: NR_ERR_INTERNAL with the reason.
+ * NR_ERR_INVALID: no dataset, or an output missing with n > 1.
+ * NR_ERR_UNSUPPORTED: n > 2^30. */
+int nr_hclust_average(nr_ctx* ctx, int32_t* id_lo, int32_t* id_hi, double* height, double* size);
+/* Device time in ms (HIP events) of the extract and all chain launches of the
+ * context's last nr_hclust_average call; 0 before the first. */
+int nr_hclust_ms(nr_ctx* ctx, double* ms);
+/* Of that call (any output may be NULL): nearest-neighbour searches made,
+ * chain launches, and device scratch bytes it allocated. */
+int nr_hclust_info(nr_ctx* ctx, int64_t* searches, int64_t* launches, int64_t* scratch_bytes);
+/* Test knob: merges per chain launch M of later nr_hclust_average calls on
+ * this context; 0 restores the default (512). A call of n nodes takes
+ * ceil((n - 1) / M) launches. It changes no result. */
+int nr_set_hclust_merges_per_launch(nr_ctx* ctx, int64_t merges);
+/* The guard's host-side arithmetic, pure host functions (no context, no GPU):
+ * the search cap 4 n + 16 of a call of n_nodes, and the message of a kernel
+ * error word (1: search cap exceeded, 2: no finite neighbour, 3: the chain
+ * outgrew the live slots) into buf (NUL-terminated); NR_ERR_INVALID for an
+ * unknown word or a buffer too small. */
+int nr_hclust_search_cap(int64_t n_nodes, int64_t* cap);
+int nr_hclust_error_message(int32_t word, char* buf, int64_t cap);
 /* The resident corr and net (n_nodes x n_nodes each, column-major) to host
  * arrays; either may be NULL. Works for a dataset made by any of the
  * set-dataset calls, before or after the Gram table is built: the pairs are
@@ -733,6 +794,46 @@ int netrep_DatasetPermutationProcedure(
     const char* const* ma_labels, int64_t n_assign, const char* const* modules, int64_t n_modules,
     int64_t n_perm, int32_t n_cores, const char* null_hypothesis, int32_t verbose, uint64_t seed,
     const uint32_t* pi, double* nulls_out, double* observed_out);
+
+/* The gene dendrogram of the handle's network as R's hclust object:
+ * nr_hclust_average on the handle's context (the definition is there), then
+ * netrep_HclustFinish. merge [(n - 1) x 2, column-major], height [n - 1],
+ * order [n]; n_repairs may be NULL. While it runs the calling thread polls
+ * the interrupt hook every 100 ms (NR_ERR_CANCELLED, between launches); the
+ * handle's dataset is unchanged and no per-batch buffer remains. */
+int netrep_DatasetHclust(netrep_dataset* d, int32_t* merge, double* height, int32_t* order, int32_t* n_repairs);
+/* Discovery order (nr_hclust_average's id_lo, id_hi, height) to R's hclust
+ * components; a pure host function (no context, no GPU).
+ *   - Monotone repair, in discovery order: h_t = max(h_t, h of each child
+ *     cluster). A no-op unless heights tie to rounding level; *n_repairs
+ *     (optional) counts the steps it raised.
+ *   - Stable sort by height: ties keep discovery order, so children always
+ *     precede parents.
+ *   - merge: singleton i becomes -(i + 1), the cluster of sorted step s
+ *     becomes s + 1; within a row two singletons stand in increasing node
+ *     index, a singleton before a cluster, two clusters in increasing step.
+ *   - order (1-based): the last merge expanded recursively, the first
+ *     column's leaves before the second's, as R derives it.
+ *   - height: the sorted heights.
+ * n = 1: merge and height are empty, order = {1}. NR_ERR_INVALID: a NULL
+ * pointer (id_lo, id_hi, height, merge may be NULL when n = 1), n < 1 or
+ * > 2^30, a NaN height, ids that are not a binary tree in construction
+ * order (each id below n + t at step t, each a child exactly once). */
+int netrep_HclustFinish(int64_t n, const int32_t* id_lo, const int32_t* id_hi, const double* height_in,
+                        int32_t* merge, double* height, int32_t* order, int32_t* n_repairs);
+/* A static cut of such a tree into module labels, after WGCNA's
+ * cutreeStatic(dendro, cutHeight, minSize); a pure host function. WGCNA is
+ * not consulted: these rules are the contract.
+ *   - Every merge with height <= cut_height is applied.
+ *   - The resulting clusters are numbered by first appearance in node order
+ *     (R's cutree).
+ *   - Clusters with fewer than min_size nodes get label 0.
+ *   - The rest are renumbered 1, 2, ... by decreasing size; ties go to the
+ *     lower cutree number.
+ * labels [n]. NR_ERR_INVALID: a NULL pointer, n < 1, a NaN, or a merge
+ * matrix whose rows refer to anything but nodes and earlier rows, once each. */
+int netrep_CutreeStatic(int64_t n, const int32_t* merge, const double* height, double cut_height,
+                        int64_t min_size, int32_t* labels);
 
 /* One-shots for glue whose call sites are separate: build the handle, make
  * the one call, release it. */

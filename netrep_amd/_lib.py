@@ -23,6 +23,7 @@ NR_ERR_OOM = 3
 NR_ERR_UNSUPPORTED = 4
 NR_ERR_CANCELLED = 5
 NR_ERR_NONFINITE = 6
+NR_ERR_INTERNAL = 7
 NR_HOST = 0
 NR_DEVICE = 1
 NR_SCALE_DATA = 1
@@ -153,6 +154,15 @@ SIGNATURES = {
     "nr_sft_ms": (_int, [_p, C.POINTER(C.c_double)]),
     "nr_sft_finite": (_int, [_p, _intp]),
     "nr_set_sft_row_groups": (_int, [_p, _int]),
+    "nr_hclust_average": (_int, [_p, _i32p, _i32p, _dp, _dp]),
+    "nr_hclust_ms": (_int, [_p, C.POINTER(C.c_double)]),
+    "nr_hclust_info": (_int, [_p, _i64p, _i64p, _i64p]),
+    "nr_set_hclust_merges_per_launch": (_int, [_p, _i64]),
+    "nr_hclust_search_cap": (_int, [_i64, _i64p]),
+    "nr_hclust_error_message": (_int, [_i32, C.c_char_p, _i64]),
+    "netrep_DatasetHclust": (_int, [_p, _i32p, _dp, _i32p, _i32p]),
+    "netrep_HclustFinish": (_int, [_i64, _i32p, _i32p, _dp, _i32p, _dp, _i32p, _i32p]),
+    "netrep_CutreeStatic": (_int, [_i64, _i32p, _dp, C.c_double, _i64, _i32p]),
     "netrep_ScaleFreeFit": (_int, [_dp, _i64, _i32, _i32, _dp]),
     "netrep_ScaleFreeBins": (_int, [_dp, _i64, _i32, _i32p]),
     "netrep_SftPowerEstimate": (_int, [_dp, _i32, C.c_double, _dp]),

@@ -767,6 +767,81 @@ class FromDataDataset:
         L.check_api(L.load().netrep_DatasetMatrices(h, _dptr(corr), _dptr(net)))
         return RMatrix(corr, self.node_names, self.node_names), RMatrix(net, self.node_names, self.node_names)
 
+    def hclust(self) -> dict:
+        """The average-linkage gene dendrogram of this dataset's network on
+        d = 1 - net (netrep_DatasetHclust), built on the GPU, as the
+        components of R's ``hclust`` object: ``merge`` ((n - 1) x 2),
+        ``height``, ``order`` (1-based), ``labels`` (the node names),
+        ``method`` "average"; ``n_repairs`` beside them. The dataset stays
+        resident and unchanged."""
+        h = self._handle()
+        n = self.n_nodes
+        merge = np.zeros((max(n - 1, 0), 2), dtype=np.int32, order="F")
+        height = np.zeros(max(n - 1, 0), dtype=np.float64)
+        order = np.zeros(n, dtype=np.int32)
+        repairs = C.c_int32()
+        L.check_api(L.load().netrep_DatasetHclust(h, _i32ptr(merge), _dptr(height), _i32ptr(order), C.byref(repairs)))
+        return {"merge": merge, "height": height, "order": order, "labels": list(self.node_names),
+                "method": "average", "n_repairs": int(repairs.value)}
+
+
+def _i32ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def hclustFinish(n: int, id_lo, id_hi, height):
+    """Discovery-order merges (``Engine.hclust_average``) to R's hclust
+    components (netrep_HclustFinish; a pure host function): ``(merge, height,
+    order, n_repairs)``."""
+    n = int(n)
+    m = max(n - 1, 0)
+    lo = np.ascontiguousarray(id_lo, dtype=np.int32)
+    hi = np.ascontiguousarray(id_hi, dtype=np.int32)
+    h_in = np.ascontiguousarray(height, dtype=np.float64)
+    if lo.shape != (m,) or hi.shape != (m,) or h_in.shape != (m,):
+        raise L.NetRepError(L.NR_ERR_INVALID, "id_lo, id_hi and height must hold n - 1 entries each")
+    merge = np.zeros((m, 2), dtype=np.int32, order="F")
+    h = np.zeros(m, dtype=np.float64)
+    order = np.zeros(max(n, 1), dtype=np.int32)
+    repairs = C.c_int32()
+    L.check_api(L.load().netrep_HclustFinish(n, _i32ptr(lo), _i32ptr(hi), _dptr(h_in), _i32ptr(merge), _dptr(h),
+                                             _i32ptr(order), C.byref(repairs)))
+    return merge, h, order, int(repairs.value)
+
+
+def cutreeStatic(tree: Mapping, cutHeight: float, minSize: int = 50) -> np.ndarray:
+    """A static cut of an hclust tree (``FromDataDataset.hclust()``, or any
+    mapping with ``merge`` and ``height``) into module labels, after WGCNA's
+    cutreeStatic (netrep_CutreeStatic; a pure host function): every merge
+    with height <= ``cutHeight`` is applied, clusters of fewer than
+    ``minSize`` nodes get 0, the rest are numbered 1, 2, ... by decreasing
+    size (ties: the cluster that appears first in node order)."""
+    merge = np.asfortranarray(np.asarray(tree["merge"], dtype=np.int32))
+    height = np.ascontiguousarray(tree["height"], dtype=np.float64)
+    m = height.shape[0]
+    if merge.shape != (m, 2):
+        raise L.NetRepError(L.NR_ERR_INVALID, "merge must be (n - 1) x 2 and height n - 1 long")
+    labels = np.zeros(m + 1, dtype=np.int32)
+    L.check_api(L.load().netrep_CutreeStatic(m + 1, _i32ptr(merge), _dptr(height), float(cutHeight), int(minSize),
+                                             _i32ptr(labels)))
+    return labels
+
+
+def DetectModulesFromData(data: RMatrix, beta: float, cutHeight: float, minSize: int = 50,
+                          networkType: str = "unsigned", corType: str = "pearson", tom: bool = True,
+                          scaleData: bool = True) -> dict:
+    """Module labels from the data matrix alone: the network (the TOM unless
+    ``tom=False``) is built on the GPU, its average-linkage dendrogram on
+    1 - net is built there too, and a static cut at ``cutHeight`` with
+    ``minSize`` gives the labels; no n x n matrix exists on the host. Returns
+    ``{"moduleAssignments": {node name: label}, "tree": ...}``: labels as
+    strings, the background "0", directly usable as ``moduleAssignments`` of
+    modulePreservationFromData; ``tree`` as ``FromDataDataset.hclust()``."""
+    with FromDataDataset(data, beta, networkType=networkType, scaleData=scaleData, tom=tom, corType=corType) as ds:
+        tree = ds.hclust()
+    labels = cutreeStatic(tree, cutHeight, minSize)
+    return {"moduleAssignments": {nm: str(int(lab)) for nm, lab in zip(tree["labels"], labels)}, "tree": tree}
+
 
 def IntermediatePropertiesFromData(dData: RMatrix, beta: float, tNodeNames, moduleAssignments, modules,
                                    networkType: str = "unsigned", scaleData: bool = False, tom: bool = False,

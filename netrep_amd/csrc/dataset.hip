@@ -10,6 +10,7 @@
 #include <set>
 
 #include "engine_internal.h"
+#include "hclust_host.h"
 #include "kernels.h"
 #include "rds_reader.h"
 
@@ -546,6 +547,128 @@ int nr_set_sft_row_groups(nr_ctx* ctx, int row_groups) {
   if (row_groups < 0 || row_groups > nr::kSftRowGroupsLimit)
     return fail(ctx, NR_ERR_INVALID, "row groups must be 0 (the default) .. " + std::to_string(nr::kSftRowGroupsLimit));
   ctx->sft_row_groups = row_groups;
+  return NR_OK;
+}
+
+int nr_hclust_average(nr_ctx* ctx, int32_t* id_lo, int32_t* id_hi, double* height, double* size) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (!ctx->ds.d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
+  // a cancellation requested before the call is honoured and consumed, as nr_run does
+  if (ctx->cancel.exchange(false)) return fail(ctx, NR_ERR_CANCELLED, "hclust cancelled");
+  const int64_t n = ctx->ds.n_nodes;
+  if (n > 1 && (!id_lo || !id_hi || !height || !size))
+    return fail(ctx, NR_ERR_INVALID, "id_lo, id_hi, height or size missing");
+  if (n > nr::kHclustMaxNodes) return fail(ctx, NR_ERR_UNSUPPORTED, "hclust: n_nodes exceeds 2^30");
+  ctx->hclust_ms = 0.0;
+  ctx->hclust_searches = ctx->hclust_launches = ctx->hclust_scratch = 0;
+  if (n < 2) return NR_OK;  // one node: no merge
+  NR_HIP(ctx, hipSetDevice(ctx->device));
+  // the table build replaces d_pairs between launches only; wait for both lanes
+  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->obs_stream) NR_HIP(ctx, hipStreamSynchronize(ctx->obs_stream));
+  // Everything on the device lives for this call only and is freed on every path.
+  struct Transient {
+    double* D = nullptr;
+    char* state = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    ~Transient() {
+      (void)hipStreamSynchronize(stream);  // nothing queued still uses what is freed
+      dfree(D);
+      dfree(state);
+      for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } t;
+  t.stream = ctx->stream;
+  const int64_t ld = nr::hclust_ld(n);
+  const size_t d_bytes = (size_t)n * (size_t)ld * sizeof(double);
+  const size_t state_bytes = nr::hclust_state_bytes(n);
+  auto oom = [&](const char* what, size_t bytes, const char* formula) {
+    (void)hipGetLastError();
+    return fail(ctx, NR_ERR_OOM,
+                std::string("hclust: allocation of the ") + std::to_string(bytes) + "-byte (" +
+                    std::to_string(bytes >> 20) + " MiB) " + what + " failed (" + formula + ")");
+  };
+  if (hipMalloc((void**)&t.D, d_bytes) != hipSuccess) {
+    t.D = nullptr;
+    return oom("working matrix", d_bytes, "8 n ld bytes, ld = n rounded up to even");
+  }
+  if (hipMalloc((void**)&t.state, state_bytes) != hipSuccess) {
+    t.state = nullptr;
+    return oom("chain state", state_bytes, "64 + 40 n bytes");
+  }
+  ctx->hclust_scratch = (int64_t)(d_bytes + state_bytes);
+  for (hipEvent_t& x : t.ev) NR_HIP(ctx, hipEventCreate(&x));
+  nr::HclustParams P = nr::hclust_params(n, t.D, t.state);
+  if (ctx->hclust_merges > 0) P.max_merges = ctx->hclust_merges;
+  double total_ms = 0.0;
+  auto timed = [&](hipError_t launched) -> hipError_t {  // between the two event records: one launch
+    hipError_t e = launched;
+    if (e == hipSuccess) e = hipEventRecord(t.ev[1], ctx->stream);
+    if (e == hipSuccess) e = hipEventSynchronize(t.ev[1]);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, t.ev[0], t.ev[1]);
+    total_ms += (double)ms;
+    return e;
+  };
+  NR_HIP(ctx, hipEventRecord(t.ev[0], ctx->stream));
+  NR_HIP(ctx, timed(nr::launch_hclust_extract(ctx->ds.d_pairs, ctx->ds.pairs_es, P, ctx->stream)));
+  // The resident dataset is not read again. Launches of at most max_merges
+  // merges each; every launch but a failing one completes its share, so the
+  // count is known ahead and bounds this loop.
+  const int64_t expected = nr::hclust_launches(n, P.max_merges);
+  long long st[nr::kHclustStateWords] = {};
+  for (int64_t launch = 0; launch < expected; ++launch) {
+    if (ctx->cancel.load()) {
+      ctx->cancel = false;
+      return fail(ctx, NR_ERR_CANCELLED, "hclust cancelled");
+    }
+    NR_HIP(ctx, hipEventRecord(t.ev[0], ctx->stream));
+    NR_HIP(ctx, timed(nr::launch_hclust_chain(P, ctx->stream)));
+    NR_HIP(ctx, hipMemcpy(st, P.st, sizeof(st), hipMemcpyDeviceToHost));
+    ++ctx->hclust_launches;
+    ctx->hclust_searches = (int64_t)st[nr::kHclustStSearches];
+    ctx->hclust_ms = total_ms;
+    if (st[nr::kHclustStError] != 0) {
+      const char* text = nr::hclust_error_text((int32_t)st[nr::kHclustStError]);
+      return fail(ctx, NR_ERR_INTERNAL,
+                  std::string("hclust: ") + (text ? text : "unknown error word") + " (after " +
+                      std::to_string(st[nr::kHclustStMerged]) + " merges and " +
+                      std::to_string(st[nr::kHclustStSearches]) + " searches)");
+    }
+    if (st[nr::kHclustStMerged] >= n - 1) break;
+  }
+  if (st[nr::kHclustStMerged] != n - 1)
+    return fail(ctx, NR_ERR_INTERNAL, "hclust: the launches ended with " + std::to_string(st[nr::kHclustStMerged]) +
+                                          " of " + std::to_string(n - 1) + " merges");
+  ctx->cancel = false;  // a cancellation that arrives after the last launch has nothing left to stop
+  const size_t m = (size_t)(n - 1);
+  NR_HIP(ctx, hipMemcpy(id_lo, P.m_lo, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  NR_HIP(ctx, hipMemcpy(id_hi, P.m_hi, m * sizeof(int32_t), hipMemcpyDeviceToHost));
+  NR_HIP(ctx, hipMemcpy(height, P.m_height, m * sizeof(double), hipMemcpyDeviceToHost));
+  NR_HIP(ctx, hipMemcpy(size, P.m_size, m * sizeof(double), hipMemcpyDeviceToHost));
+  return NR_OK;
+}
+
+int nr_hclust_ms(nr_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return NR_ERR_INVALID;
+  *ms = ctx->hclust_ms;
+  return NR_OK;
+}
+
+int nr_hclust_info(nr_ctx* ctx, int64_t* searches, int64_t* launches, int64_t* scratch_bytes) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (searches) *searches = ctx->hclust_searches;
+  if (launches) *launches = ctx->hclust_launches;
+  if (scratch_bytes) *scratch_bytes = ctx->hclust_scratch;
+  return NR_OK;
+}
+
+int nr_set_hclust_merges_per_launch(nr_ctx* ctx, int64_t merges) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (merges < 0) return fail(ctx, NR_ERR_INVALID, "merges per launch must be 0 (the default) or more");
+  ctx->hclust_merges = merges;
   return NR_OK;
 }
 

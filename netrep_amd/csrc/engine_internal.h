@@ -48,6 +48,10 @@ struct nr_ctx {
   double sft_ms = 0.0;           // device time of the last call's kernels (0: none yet)
   int sft_finite = 1;            // the last call's connectivities were all finite
   int sft_row_groups = 0;        // nr_set_sft_row_groups (0: the default, nr::sft_row_groups(n))
+  // nr_hclust_average (it reads the resident net once and writes nothing resident)
+  int64_t hclust_merges = 0;     // nr_set_hclust_merges_per_launch (0: the default, nr::kHclustMergesPerLaunch)
+  double hclust_ms = 0.0;        // device time of the last call's extract and chain launches
+  int64_t hclust_searches = 0, hclust_launches = 0, hclust_scratch = 0;  // of the last call (nr_hclust_info)
   int64_t table_checked = -1;    // modules_serial the Gram-table decision was made for
   int64_t data_gen = 0;          // bumped by every dataset change (reset_dataset)
   int64_t modules_gen = -1;      // data_gen the modules were validated against

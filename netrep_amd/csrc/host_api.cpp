@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/netrep_gpu.h"
+#include "hclust_host.h"
 #include "rds_reader.h"
 #include "sft_fit.h"
 
@@ -1387,6 +1388,78 @@ int netrep_DatasetPermutationProcedure(const netrep_disc_props* disc, netrep_dat
     (void)nr_ctx_set_host_threads(c, d->n_cores != 0 ? d->n_cores : nr_get_host_threads());
   }
   return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_HclustFinish(int64_t n, const int32_t* id_lo, const int32_t* id_hi, const double* height_in,
+                        int32_t* merge, double* height, int32_t* order, int32_t* n_repairs) try {
+  if (n < 1 || !order || (n > 1 && (!id_lo || !id_hi || !height_in || !merge || !height)))
+    return set_err(NR_ERR_INVALID, "invalid arguments to HclustFinish");
+  if (!nr::hclust_finish(n, id_lo, id_hi, height_in, merge, height, order, n_repairs))
+    return set_err(NR_ERR_INVALID, "invalid arguments to HclustFinish (not a binary tree in construction order, "
+                                   "a NaN height, or more than 2^30 nodes)");
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_CutreeStatic(int64_t n, const int32_t* merge, const double* height, double cut_height, int64_t min_size,
+                        int32_t* labels) try {
+  if (n < 1 || !labels || (n > 1 && (!merge || !height)))
+    return set_err(NR_ERR_INVALID, "invalid arguments to CutreeStatic");
+  if (!nr::cutree_static(n, merge, height, cut_height, min_size, labels))
+    return set_err(NR_ERR_INVALID, "invalid arguments to CutreeStatic (a NaN, or merge is not an hclust merge matrix)");
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetHclust(netrep_dataset* d, int32_t* merge, double* height, int32_t* order,
+                         int32_t* n_repairs) try {
+  if (!d) return no_dataset("DatasetHclust");
+  if (!order || (d->n_nodes > 1 && (!merge || !height)))
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetHclust");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  nr_ctx* const c = d->ctx.get();
+  const size_t m = (size_t)(d->n_nodes - 1);
+  std::vector<int32_t> id_lo(m), id_hi(m);
+  std::vector<double> h(m), size(m);
+  // The chain runs on a worker thread; the calling thread polls the interrupt
+  // hook every 100 ms, as the permutation path does, and returns as soon as
+  // the worker is done.
+  std::atomic<bool> finished{false};
+  int rc = NR_OK;
+  std::thread worker([&]() {
+    rc = nr_hclust_average(c, id_lo.data(), id_hi.data(), h.data(), size.data());
+    finished.store(true);
+  });
+  bool interrupted = false;
+  for (int tick = 0; !finished.load(); ++tick) {
+    std::this_thread::sleep_for(std::chrono::milliseconds(1));
+    if (tick % 100 == 99 && !interrupted && interrupt_requested()) {
+      interrupted = true;
+      nr_cancel(c);
+    }
+  }
+  worker.join();
+  if (interrupted && rc == NR_OK) {
+    // A cancellation that reached the context after its last launch is still
+    // pending: a call that finds one consumes it and returns at once, so the
+    // next call on the handle starts clean, and the interrupt is reported.
+    if (nr_hclust_average(c, nullptr, nullptr, nullptr, nullptr) == NR_ERR_CANCELLED) rc = NR_ERR_CANCELLED;
+  }
+  if (rc) return ctx_err(rc, c);
+  if (!nr::hclust_finish(d->n_nodes, id_lo.data(), id_hi.data(), h.data(), merge, height, order, n_repairs))
+    return set_err(NR_ERR_INTERNAL, "hclust: the device returned merges that are not a binary tree");
+  return NR_OK;
 } catch (const std::bad_alloc&) {
   return set_err(NR_ERR_OOM, "host memory allocation failed");
 } catch (const std::exception& e) {

@@ -233,6 +233,32 @@ size_t sft_result_offset(int64_t n, int n_powers, int row_groups);
 size_t sft_scratch_bytes(int64_t n, int n_powers, int row_groups);
 hipError_t launch_soft_connectivity(const double* X, int64_t S, int64_t n, int net_type, const double* powers,
                                     int n_powers, int row_groups, double* scratch, int* flags, hipStream_t st);
+// The average-linkage dendrogram of the resident network (hclust.hip,
+// nr_hclust_average). hclust_extract_kernel writes the working matrix D
+// (column-major, n columns of ld = hclust_ld(n) doubles: 1 - net, +inf on the
+// diagonal and in the padding row) from the pairs in either layout, and the
+// chain's initial state; hclust_chain_kernel, one workgroup of 1,024 threads,
+// runs the nearest-neighbour chain for at most max_merges merges per launch
+// and resumes from the state block. state: hclust_state_bytes(n) bytes, laid
+// out by hclust_params.
+enum { kHclustStChainLen = 0, kHclustStMerged, kHclustStSearches, kHclustStError, kHclustStFirstLive,
+       kHclustStateWords = 8 };
+struct HclustParams {
+  double* D;                   // n x ld working matrix
+  int64_t n, ld;
+  long long* st;               // [kHclustStateWords] state words
+  double* size;                // [n] cluster size of each slot (0: retired)
+  int32_t* chain;              // [n] the chain's stack of slots
+  int32_t* id;                 // [n] cluster id of each slot
+  int32_t *m_lo, *m_hi;        // [n - 1] emitted merges, discovery order
+  double *m_height, *m_size;
+  int64_t max_merges;          // merges per launch
+  int64_t search_cap;          // nearest-neighbour searches per call (hclust_search_cap)
+};
+size_t hclust_state_bytes(int64_t n);
+HclustParams hclust_params(int64_t n, double* D, void* state);
+hipError_t launch_hclust_extract(const double2* pairs, int es, const HclustParams& P, hipStream_t st);
+hipError_t launch_hclust_chain(const HclustParams& P, hipStream_t st);
 // corr[e], net[e] (either may be NULL) = elements [first, first + len) of a
 // pair array in layout es (1, or 2: the Gram table).
 hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,

@@ -192,6 +192,41 @@ class Engine:
         ``soft_connectivity`` calls; 0 restores the default."""
         self._check(self._lib.nr_set_sft_row_groups(self._h, int(row_groups)))
 
+    def hclust_average(self):
+        """The average-linkage dendrogram of the resident dataset's nodes on
+        d = 1 - net (nr_hclust_average; include/netrep_gpu.h has the rules),
+        raw: ``(id_lo, id_hi, height, size)`` of the n - 1 merges in discovery
+        order, ids 0 .. n-1 nodes and n + t the cluster of step t. The
+        resident dataset is not changed."""
+        n, _s = self.shape()
+        m = max(n - 1, 0)
+        id_lo = np.zeros(m, dtype=np.int32)
+        id_hi = np.zeros(m, dtype=np.int32)
+        height = np.zeros(m, dtype=np.float64)
+        size = np.zeros(m, dtype=np.float64)
+        self._check(self._lib.nr_hclust_average(self._h, id_lo.ctypes.data_as(L._i32p), id_hi.ctypes.data_as(L._i32p),
+                                                _ptr(height), _ptr(size)))
+        return id_lo, id_hi, height, size
+
+    def hclust_ms(self) -> float:
+        """Device time in ms of the extract and all chain launches of this
+        engine's last ``hclust_average`` call (nr_hclust_ms)."""
+        ms = C.c_double()
+        self._check(self._lib.nr_hclust_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def hclust_info(self) -> dict:
+        """Of the last ``hclust_average`` call (nr_hclust_info): nearest-
+        neighbour ``searches``, chain ``launches``, device ``scratch_bytes``."""
+        s, l, b = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.nr_hclust_info(self._h, C.byref(s), C.byref(l), C.byref(b)))
+        return {"searches": int(s.value), "launches": int(l.value), "scratch_bytes": int(b.value)}
+
+    def set_hclust_merges_per_launch(self, merges: int):
+        """Test knob (nr_set_hclust_merges_per_launch): merges per chain
+        launch of later ``hclust_average`` calls; 0 restores the default."""
+        self._check(self._lib.nr_set_hclust_merges_per_launch(self._h, int(merges)))
+
     def set_dataset_files(self, corr_path, net_path, data_path=None, objects=(None, None, None),
                           scale_data=True):
         """disk.matrix files (saveRDS output, or objects of a save() archive)
