@@ -271,6 +271,45 @@ int nr_set_hclust_merges_per_launch(nr_ctx* ctx, int64_t merges);
  * unknown word or a buffer too small. */
 int nr_hclust_search_cap(int64_t n_nodes, int64_t* cap);
 int nr_hclust_error_message(int32_t word, char* buf, int64_t cap);
+/* Module eigengenes on explicit index sets (CSR, as nr_module_vectors takes
+ * them): the summary-profile half of nr_module_vectors and nothing else --
+ * the same kernels, module order and size classes, so eigengenes,
+ * var_explained and contribution carry the bits of its summary, coherence and
+ * contribution -- with no network statistics and none of their allocations.
+ * The eigengene of a module is NetRep's summary profile (src/netStats.cpp:
+ * 217-250): the first left singular vector of the module's columns of the
+ * resident data, unit length, its sign chosen so that it correlates
+ * positively with the mean of the columns: WGCNA's moduleEigengenes for a
+ * scaled data block. var_explained is the module's coherence (the mean
+ * squared contribution), contribution each node's correlation with its own
+ * module's eigengene, the in-module kME, in CSR order; it may be NULL.
+ * eigengenes [n_samples x n_mod, column-major], var_explained [n_mod].
+ * The eigengenes also stay in a device buffer of the context until the next
+ * call, a dataset change or nr_release_scratch; the buffer counts in
+ * nr_scratch_bytes. Nothing resident is written.
+ * NR_ERR_INVALID: n_mod < 1, a missing array, no dataset or one without data,
+ * an empty module, an index outside the dataset. */
+int nr_module_eigengenes(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const int32_t* idx,
+                         double* eigengenes, double* var_explained, double* contribution);
+/* Module membership of every node of the resident dataset:
+ *   kME[i, m] = sum_s (x_si - mu_i) e^_sm / sqrt(sum_s (x_si - mu_i)^2),
+ * x_i column i of the resident data exactly as stored (scaled or not), mu_i
+ * its mean, e^_m eigengene m centred and scaled to unit length: the Pearson
+ * correlation of node i with eigengene m. kme [n_nodes x n_mod, column-major].
+ * eigengenes NULL: the n_mod eigengenes the context keeps from its last
+ * nr_module_eigengenes call on this dataset (no upload); else n_mod host
+ * columns [n_samples x n_mod], uploaded (counted in nr_h2d_bytes).
+ * Every sum runs over s in increasing order per thread or lane set fixed by
+ * n_samples alone and there are no atomics: a cell's bits do not depend on
+ * n_mod, on the eigengene's place in the call, or on the other nodes.
+ * Device scratch for the call: 8 n_samples n_mod (twice with an upload) and
+ * 8 n_nodes n_mod bytes, freed before it returns. Nothing resident is written.
+ * NR_ERR_INVALID: n_mod < 1, kme missing, no dataset or one without data,
+ * n_samples < 3, or eigengenes NULL with no matching kept eigengenes. */
+int nr_module_membership(nr_ctx* ctx, int32_t n_mod, const double* eigengenes, double* kme);
+/* Device time in ms (HIP events) of the two kernels of the context's last
+ * nr_module_membership call; 0 before the first. */
+int nr_membership_ms(nr_ctx* ctx, double* ms);
 /* The resident corr and net (n_nodes x n_nodes each, column-major) to host
  * arrays; either may be NULL. Works for a dataset made by any of the
  * set-dataset calls, before or after the Gram table is built: the pairs are
@@ -834,6 +873,92 @@ int netrep_HclustFinish(int64_t n, const int32_t* id_lo, const int32_t* id_hi, c
  * matrix whose rows refer to anything but nodes and earlier rows, once each. */
 int netrep_CutreeStatic(int64_t n, const int32_t* merge, const double* height, double cut_height,
                         int64_t min_size, int32_t* labels);
+
+/* What follows a cut: eigengenes, module membership, the merging of close
+ * modules and the kME trimming. Neither R nor WGCNA is consulted: these rules
+ * are the contract. Labels are int32 [n_nodes] in the dataset's node order, 0
+ * unassigned, positive values modules (what netrep_CutreeStatic writes);
+ * "modules" are the distinct positive labels in increasing order, M of them.
+ *
+ * The eigengene tree (netrep_EigengeneGroups; a pure host function). eig
+ * [S x M, column-major].
+ *   - c = cor(E), Pearson over samples: each column's mean (its sum in sample
+ *     order over S), the centred values z, their sum of squares ss, and
+ *     c_ab = sum_s z_sa z_sb / sqrt(ss_a ss_b) clamped to [-1, 1]; d = 1 - c.
+ *     Every product, sum, division and root is rounded to fp64 on its own.
+ *   - Average linkage by the Lance-Williams update of nr_hclust_average,
+ *     d(k, a u b) = (s_a d(k, a) + s_b d(k, b)) / (s_a + s_b), never fused.
+ *   - Each step merges the globally closest pair of clusters; a cluster is
+ *     indexed by its lowest column, and ties go to the lowest (lower index,
+ *     higher index) pair. height_out [M - 1]: the heights in merge order.
+ *   - Groups: the clusters left after every merge with height <= cut_height.
+ *     group_out [M]: the 0-based index of the first column of each column's
+ *     group.
+ * M = 1: one group, no height. NR_ERR_INVALID: a NULL pointer, S < 2, M < 1,
+ * cut_height outside [0, 2] or NaN, a non-finite or constant column. */
+int netrep_EigengeneGroups(const double* eig, int64_t n_samples, int64_t n_mod, double cut_height,
+                           int32_t* group_out, double* height_out);
+/* One merge step (a pure host function): every node of module
+ * module_labels[m] gets the label module_labels[group[m]], the label of the
+ * first module of its group (under netrep_CutreeStatic's numbering the lowest
+ * label and hence the largest module); 0 never changes. relabel != 0: the
+ * surviving modules are then renumbered 1, 2, ... by decreasing size, ties to
+ * the lower old label. labels_out may be labels_in. NR_ERR_INVALID: a NULL
+ * pointer, a negative label, a positive label missing from module_labels, a
+ * module label that is not positive or given twice, group[m] outside 0 .. m. */
+int netrep_MergeLabels(int64_t n, const int32_t* labels_in, int64_t n_mod, const int32_t* module_labels,
+                       const int32_t* group, int32_t relabel, int32_t* labels_out);
+/* The kME trimming of WGCNA's blockwiseModules, in-module kME only, one pass,
+ * no relabelling (a pure host function). kme_own [n]: each node's correlation
+ * with its own module's eigengene (ignored for label 0). Per module:
+ *   - fewer than min_core_kme_size nodes with kme_own > min_core_kme: the
+ *     whole module goes to 0 (min_core_kme_size < 0: the default, min_size / 3,
+ *     as a count: rounded up);
+ *   - otherwise its nodes with kme_own < min_kme_to_stay go to 0;
+ *   - a module then left with fewer than min_size nodes goes to 0.
+ * WGCNA's defaults are 0.3, 0.5 and min_size / 3. Its reassignment by kME
+ * p-value (reassignThreshold) is not offered. NR_ERR_INVALID: a NULL pointer,
+ * n < 1, a negative label, a NaN threshold. */
+int netrep_TrimModulesKME(int64_t n, const int32_t* labels_in, const double* kme_own, double min_kme_to_stay,
+                          double min_core_kme, int64_t min_core_kme_size, int64_t min_size, int32_t* labels_out);
+/* On the handle. Common to the four: labels [n_nodes] as above;
+ * NR_ERR_INVALID with a text naming it for a NULL argument, a negative
+ * label, or a label vector with no positive label; the interrupt hook is
+ * polled before every device call (NR_ERR_CANCELLED); the handle's dataset
+ * is unchanged and no per-batch buffer remains.
+ * The eigengenes are those of the data as the handle holds them: WGCNA's
+ * moduleEigengenes for a handle built with scale_data, the unscaled data's
+ * otherwise.
+ * netrep_DatasetModuleEigengenes: nr_module_eigengenes of the label vector's
+ * modules. n_mod_out and module_labels_out [M] (optional), eigengenes
+ * [S x M, column-major], var_explained [M], kme_own [n_nodes] in node order
+ * (optional; NA for label 0). The caller sizes the outputs by its own count
+ * of distinct positive labels. */
+int netrep_DatasetModuleEigengenes(netrep_dataset* d, const int32_t* labels, int32_t* n_mod_out,
+                                   int32_t* module_labels_out, double* eigengenes, double* var_explained,
+                                   double* kme_own);
+/* The module-membership table: the eigengenes as above, then
+ * nr_module_membership on the context's copy of them. kme [n_nodes x M,
+ * column-major]. */
+int netrep_DatasetModuleMembership(netrep_dataset* d, const int32_t* labels, double* kme);
+/* WGCNA's mergeCloseModules with iterate = TRUE. A round computes the
+ * eigengenes of the current labels, builds their tree, cuts it at cut_height
+ * (netrep_EigengeneGroups) and merges (netrep_MergeLabels, no relabelling);
+ * rounds repeat until one merges nothing or one module is left: at most
+ * M - 1 rounds merge. *n_rounds_out: the rounds that merged something.
+ * relabel != 0: the final labels go through the renumbering by size.
+ * The last round (the one that merged nothing, on the final modules) is
+ * reported through the optional outputs: *n_mod_last_out the final module
+ * count M', eigengenes_last_out [S x M', at most S x M], its columns in the
+ * order of the returned labels' modules, heights_last_out [M' - 1, at most
+ * M - 1] its tree's heights (all above cut_height).
+ * NR_ERR_INVALID also for cut_height outside [0, 2] or NaN. */
+int netrep_DatasetMergeCloseModules(netrep_dataset* d, const int32_t* labels_in, double cut_height, int32_t relabel,
+                                    int32_t* labels_out, int32_t* n_rounds_out, int32_t* n_mod_last_out,
+                                    double* eigengenes_last_out, double* heights_last_out);
+/* netrep_TrimModulesKME with kme_own from the handle (netrep_DatasetModuleEigengenes). */
+int netrep_DatasetTrimModules(netrep_dataset* d, const int32_t* labels_in, double min_kme_to_stay,
+                              double min_core_kme, int64_t min_core_kme_size, int64_t min_size, int32_t* labels_out);
 
 /* One-shots for glue whose call sites are separate: build the handle, make
  * the one call, release it. */

@@ -13,7 +13,8 @@ from .api import (CheckFinite, IntermediateProperties, IntermediatePropertiesNoD
                   PrefetchTestDataset, DiscardPrefetch, ReleaseResident, h2d_bytes, PermutationProcedureFiles, RMatrix,
                   PermutationProcedureFromData, BuildNetwork, PickSoftThreshold, ScaleFreeFit,
                   FromDataDataset, IntermediatePropertiesFromData, NetPropsFromData, modulePreservationFromData,
-                  DetectModulesFromData, cutreeStatic, hclustFinish, read_rds_matrix, Scale, STATNAMES, STATNAMES_NODATA,
+                  DetectModulesFromData, cutreeStatic, hclustFinish, eigengeneGroups, mergeLabels, trimModulesKME,
+                  read_rds_matrix, Scale, STATNAMES, STATNAMES_NODATA,
                   set_interrupt_hook)
 from .engine import Engine, device_count, prp_table  # noqa: F401
 
@@ -24,4 +25,5 @@ __all__ = ["CheckFinite", "IntermediateProperties", "IntermediatePropertiesNoDat
            "DiscardPrefetch", "ReleaseResident", "h2d_bytes", "PermutationProcedureFiles", "read_rds_matrix",
            "PermutationProcedureFromData", "BuildNetwork", "PickSoftThreshold", "ScaleFreeFit",
            "FromDataDataset", "IntermediatePropertiesFromData", "NetPropsFromData",
-           "modulePreservationFromData", "DetectModulesFromData", "cutreeStatic", "hclustFinish"]
+           "modulePreservationFromData", "DetectModulesFromData", "cutreeStatic", "hclustFinish",
+           "eigengeneGroups", "mergeLabels", "trimModulesKME"]

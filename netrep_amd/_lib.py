@@ -163,6 +163,16 @@ SIGNATURES = {
     "netrep_DatasetHclust": (_int, [_p, _i32p, _dp, _i32p, _i32p]),
     "netrep_HclustFinish": (_int, [_i64, _i32p, _i32p, _dp, _i32p, _dp, _i32p, _i32p]),
     "netrep_CutreeStatic": (_int, [_i64, _i32p, _dp, C.c_double, _i64, _i32p]),
+    "nr_module_eigengenes": (_int, [_p, _i32, _i64p, _i32p, _dp, _dp, _dp]),
+    "nr_module_membership": (_int, [_p, _i32, _dp, _dp]),
+    "nr_membership_ms": (_int, [_p, C.POINTER(C.c_double)]),
+    "netrep_EigengeneGroups": (_int, [_dp, _i64, _i64, C.c_double, _i32p, _dp]),
+    "netrep_MergeLabels": (_int, [_i64, _i32p, _i64, _i32p, _i32p, _i32, _i32p]),
+    "netrep_TrimModulesKME": (_int, [_i64, _i32p, _dp, C.c_double, C.c_double, _i64, _i64, _i32p]),
+    "netrep_DatasetModuleEigengenes": (_int, [_p, _i32p, _i32p, _i32p, _dp, _dp, _dp]),
+    "netrep_DatasetModuleMembership": (_int, [_p, _i32p, _dp]),
+    "netrep_DatasetMergeCloseModules": (_int, [_p, _i32p, C.c_double, _i32, _i32p, _i32p, _i32p, _dp, _dp]),
+    "netrep_DatasetTrimModules": (_int, [_p, _i32p, C.c_double, C.c_double, _i64, _i64, _i32p]),
     "netrep_ScaleFreeFit": (_int, [_dp, _i64, _i32, _i32, _dp]),
     "netrep_ScaleFreeBins": (_int, [_dp, _i64, _i32, _i32p]),
     "netrep_SftPowerEstimate": (_int, [_dp, _i32, C.c_double, _dp]),

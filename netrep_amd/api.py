@@ -785,8 +785,136 @@ class FromDataDataset:
                 "method": "average", "n_repairs": int(repairs.value)}
 
 
+    # -- what follows a cut: eigengenes, membership, merging, trimming ------
+    def _labels(self, labels) -> np.ndarray:
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if lab.shape != (self.n_nodes,):
+            raise L.NetRepError(L.NR_ERR_INVALID, "labels must hold one integer per node, in node order")
+        return lab
+
+    def module_eigengenes(self, labels) -> dict:
+        """The eigengene of every module of ``labels`` (one integer per node
+        in node order, 0 unassigned) on the GPU (netrep_DatasetModuleEigengenes):
+        ``modules`` (the distinct positive labels, increasing), ``eigengenes``
+        (S x M), ``varExplained`` (M) and ``kME`` (n: each node's correlation
+        with its own module's eigengene, NaN for label 0). The eigengene is
+        that of the resident data: WGCNA's ``moduleEigengenes`` for a handle
+        built with ``scaleData=True``; with ``False`` it is the unscaled
+        data's."""
+        h = self._handle()
+        lab = self._labels(labels)
+        m = max(int(np.unique(lab[lab > 0]).size), 1)
+        mods = np.zeros(m, dtype=np.int32)
+        eig = np.zeros((self.n_samples, m), order="F")
+        ve = np.zeros(m)
+        own = np.zeros(self.n_nodes)
+        n_mod = C.c_int32()
+        L.check_api(L.load().netrep_DatasetModuleEigengenes(h, _i32ptr(lab), C.byref(n_mod), _i32ptr(mods), _dptr(eig),
+                                                            _dptr(ve), _dptr(own)))
+        return {"modules": mods, "eigengenes": eig, "varExplained": ve, "kME": own}
+
+    def module_membership(self, labels) -> RMatrix:
+        """The module-membership table kME, the correlation of every node
+        with every module eigengene of ``labels``, computed on the GPU from
+        the resident data (netrep_DatasetModuleMembership): n rows named by
+        node, columns ``"kME<label>"``. Eigengenes as ``module_eigengenes``."""
+        h = self._handle()
+        lab = self._labels(labels)
+        mods = np.unique(lab[lab > 0])
+        kme = np.zeros((self.n_nodes, max(int(mods.size), 1)), order="F")
+        L.check_api(L.load().netrep_DatasetModuleMembership(h, _i32ptr(lab), _dptr(kme)))
+        return RMatrix(kme, list(self.node_names), [f"kME{int(m)}" for m in mods])
+
+    def merge_close_modules(self, labels, cutHeight: float = 0.25, relabel: bool = True) -> dict:
+        """WGCNA's ``mergeCloseModules`` (iterate = TRUE) on the handle
+        (netrep_DatasetMergeCloseModules; include/netrep_gpu.h has the
+        rules): modules whose eigengenes are closer than ``cutHeight`` on
+        1 - cor in the average-linkage tree are merged, round after round,
+        until a round merges nothing. ``labels`` the merged labels
+        (renumbered 1, 2, ... by decreasing size with ``relabel``), ``rounds``
+        the rounds that merged something, ``eigengenes`` (S x M') of the
+        final modules in their label order, ``heights`` (M' - 1) of their
+        tree."""
+        h = self._handle()
+        lab = self._labels(labels)
+        m = max(int(np.unique(lab[lab > 0]).size), 1)
+        out = np.zeros(self.n_nodes, dtype=np.int32)
+        eig = np.zeros((self.n_samples, m), order="F")
+        heights = np.zeros(max(m - 1, 1))
+        rounds, m_last = C.c_int32(), C.c_int32()
+        L.check_api(L.load().netrep_DatasetMergeCloseModules(h, _i32ptr(lab), float(cutHeight), int(bool(relabel)),
+                                                             _i32ptr(out), C.byref(rounds), C.byref(m_last),
+                                                             _dptr(eig), _dptr(heights)))
+        ml = int(m_last.value)
+        return {"labels": out, "rounds": int(rounds.value), "eigengenes": np.asfortranarray(eig[:, :ml]),
+                "heights": heights[:max(ml - 1, 0)].copy()}
+
+    def trim_modules(self, labels, minSize: int, minKMEtoStay: float = 0.3, minCoreKME: float = 0.5,
+                     minCoreKMESize=None) -> np.ndarray:
+        """The kME trimming of WGCNA's ``blockwiseModules``, in-module kME
+        only (netrep_DatasetTrimModules): a module with fewer than
+        ``minCoreKMESize`` (default ``minSize / 3``) nodes of kME above
+        ``minCoreKME`` is dissolved, otherwise its nodes of kME below
+        ``minKMEtoStay`` go to 0, and a module left under ``minSize`` nodes
+        is dissolved. One pass, no relabelling; the reassignment by kME
+        p-value (``reassignThreshold``) is not offered."""
+        h = self._handle()
+        lab = self._labels(labels)
+        out = np.zeros(self.n_nodes, dtype=np.int32)
+        core = -1 if minCoreKMESize is None else int(minCoreKMESize)
+        L.check_api(L.load().netrep_DatasetTrimModules(h, _i32ptr(lab), float(minKMEtoStay), float(minCoreKME), core,
+                                                       int(minSize), _i32ptr(out)))
+        return out
+
+
 def _i32ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def eigengeneGroups(eigengenes, cutHeight: float):
+    """The eigengene tree and its cut (netrep_EigengeneGroups; a pure host
+    function): ``(group, heights)`` of an (S x M) eigengene matrix -- the
+    0-based index of the first module of every module's group, and the M - 1
+    average-linkage heights on 1 - cor in merge order."""
+    e = np.asfortranarray(np.asarray(eigengenes, dtype=np.float64))
+    if e.ndim != 2:
+        raise L.NetRepError(L.NR_ERR_INVALID, "eigengenes must be a samples x modules matrix")
+    s, m = e.shape
+    group = np.zeros(max(m, 1), dtype=np.int32)
+    heights = np.zeros(max(m - 1, 1))
+    L.check_api(L.load().netrep_EigengeneGroups(_dptr(e), s, m, float(cutHeight), _i32ptr(group), _dptr(heights)))
+    return group[:m], heights[:max(m - 1, 0)]
+
+
+def mergeLabels(labels, moduleLabels, group, relabel: bool = False) -> np.ndarray:
+    """One merge step (netrep_MergeLabels; a pure host function): nodes of
+    ``moduleLabels[m]`` get ``moduleLabels[group[m]]``; with ``relabel`` the
+    result is renumbered 1, 2, ... by decreasing size."""
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    mods = np.ascontiguousarray(moduleLabels, dtype=np.int32)
+    grp = np.ascontiguousarray(group, dtype=np.int32)
+    if lab.ndim != 1 or mods.shape != grp.shape or mods.ndim != 1:
+        raise L.NetRepError(L.NR_ERR_INVALID, "labels, moduleLabels and group must be vectors, the last two alike")
+    out = np.zeros(max(lab.size, 1), dtype=np.int32)
+    L.check_api(L.load().netrep_MergeLabels(lab.size, _i32ptr(lab), mods.size, _i32ptr(mods), _i32ptr(grp),
+                                            int(bool(relabel)), _i32ptr(out)))
+    return out[:lab.size]
+
+
+def trimModulesKME(labels, kME, minSize: int, minKMEtoStay: float = 0.3, minCoreKME: float = 0.5,
+                   minCoreKMESize=None) -> np.ndarray:
+    """The kME trimming on host arrays (netrep_TrimModulesKME; a pure host
+    function): ``kME`` each node's correlation with its own module's
+    eigengene. Rules as ``FromDataDataset.trim_modules``."""
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    own = np.ascontiguousarray(kME, dtype=np.float64)
+    if lab.ndim != 1 or own.shape != lab.shape:
+        raise L.NetRepError(L.NR_ERR_INVALID, "labels and kME must be vectors of one length")
+    out = np.zeros(max(lab.size, 1), dtype=np.int32)
+    core = -1 if minCoreKMESize is None else int(minCoreKMESize)
+    L.check_api(L.load().netrep_TrimModulesKME(lab.size, _i32ptr(lab), _dptr(own), float(minKMEtoStay),
+                                               float(minCoreKME), core, int(minSize), _i32ptr(out)))
+    return out[:lab.size]
 
 
 def hclustFinish(n: int, id_lo, id_hi, height):
@@ -829,18 +957,45 @@ def cutreeStatic(tree: Mapping, cutHeight: float, minSize: int = 50) -> np.ndarr
 
 def DetectModulesFromData(data: RMatrix, beta: float, cutHeight: float, minSize: int = 50,
                           networkType: str = "unsigned", corType: str = "pearson", tom: bool = True,
-                          scaleData: bool = True) -> dict:
+                          scaleData: bool = True, mergeCutHeight: Optional[float] = None,
+                          minKMEtoStay: Optional[float] = None, minCoreKME: float = 0.5,
+                          minCoreKMESize: Optional[int] = None) -> dict:
     """Module labels from the data matrix alone: the network (the TOM unless
     ``tom=False``) is built on the GPU, its average-linkage dendrogram on
     1 - net is built there too, and a static cut at ``cutHeight`` with
     ``minSize`` gives the labels; no n x n matrix exists on the host. Returns
     ``{"moduleAssignments": {node name: label}, "tree": ...}``: labels as
     strings, the background "0", directly usable as ``moduleAssignments`` of
-    modulePreservationFromData; ``tree`` as ``FromDataDataset.hclust()``."""
+    modulePreservationFromData; ``tree`` as ``FromDataDataset.hclust()``.
+    With ``minKMEtoStay`` and / or ``mergeCutHeight`` the cut is followed, on
+    the same resident dataset, by the kME trimming
+    (``FromDataDataset.trim_modules`` with ``minSize``, ``minCoreKME``,
+    ``minCoreKMESize``) and then the merging of close modules
+    (``merge_close_modules`` at ``mergeCutHeight``, relabelled by size), in
+    that order; the result gains ``unmergedAssignments`` (the labels before
+    the merge, as strings), ``eigengenes`` (S x M of the final modules) and
+    ``rounds``. With both ``None`` nothing else runs."""
     with FromDataDataset(data, beta, networkType=networkType, scaleData=scaleData, tom=tom, corType=corType) as ds:
         tree = ds.hclust()
-    labels = cutreeStatic(tree, cutHeight, minSize)
-    return {"moduleAssignments": {nm: str(int(lab)) for nm, lab in zip(tree["labels"], labels)}, "tree": tree}
+        labels = cutreeStatic(tree, cutHeight, minSize)
+        if mergeCutHeight is None and minKMEtoStay is None:
+            extra = {}
+        else:
+            if minKMEtoStay is not None and (labels > 0).any():
+                labels = ds.trim_modules(labels, minSize, minKMEtoStay, minCoreKME, minCoreKMESize)
+            unmerged = labels
+            extra = {"unmergedAssignments": {nm: str(int(lab)) for nm, lab in zip(tree["labels"], unmerged)},
+                     "eigengenes": np.zeros((ds.n_samples, 0), order="F"), "rounds": 0}
+            if (labels > 0).any():
+                if mergeCutHeight is not None:
+                    merged = ds.merge_close_modules(labels, mergeCutHeight, relabel=True)
+                    labels = merged["labels"]
+                    extra.update(eigengenes=merged["eigengenes"], rounds=merged["rounds"])
+                else:
+                    extra.update(eigengenes=ds.module_eigengenes(labels)["eigengenes"])
+    out = {"moduleAssignments": {nm: str(int(lab)) for nm, lab in zip(tree["labels"], labels)}, "tree": tree}
+    out.update(extra)
+    return out
 
 
 def IntermediatePropertiesFromData(dData: RMatrix, beta: float, tNodeNames, moduleAssignments, modules,

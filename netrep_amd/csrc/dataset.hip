@@ -672,6 +672,102 @@ int nr_set_hclust_merges_per_launch(nr_ctx* ctx, int64_t merges) {
   return NR_OK;
 }
 
+int nr_module_eigengenes(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const int32_t* idx, double* eigengenes,
+                         double* var_explained, double* contribution) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (n_mod < 1 || !node_off || !idx || !eigengenes || !var_explained)
+    return fail(ctx, NR_ERR_INVALID, "n_mod < 1, or node_off, idx, eigengenes or var_explained missing");
+  if (!ctx->ds.d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
+  if (!ctx->ds.d_data) return fail(ctx, NR_ERR_INVALID, "eigengenes need a dataset with data");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  NR_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->eig_n_mod = 0;  // valid again only once everything below has succeeded
+  const int64_t S = ctx->ds.n_samples;
+  ModuleSets ms;
+  double *d_nc = nullptr, *d_coh = nullptr;
+  int rc = upload_module_sets(ctx, n_mod, node_off, idx, ms);
+  if (!rc) rc = ensure(ctx, ctx->d_eig, ctx->eig_cap, (size_t)n_mod * (size_t)S);
+  if (!rc) {
+    hipError_t e = hipMalloc((void**)&d_nc, (size_t)ms.nodes * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_coh, (size_t)n_mod * sizeof(double));
+    if (e != hipSuccess) rc = hip_fail(ctx, e, "hipMalloc module eigengenes");
+  }
+  if (!rc) rc = launch_module_profiles(ctx, ms, ctx->d_eig, d_nc, d_coh);
+  if (!rc) {
+    auto d2h = [&](double* h, const double* d, int64_t n) {
+      return h ? hipMemcpyAsync(h, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) : hipSuccess;
+    };
+    hipError_t e = d2h(eigengenes, ctx->d_eig, (int64_t)n_mod * S);
+    if (e == hipSuccess) e = d2h(var_explained, d_coh, n_mod);
+    if (e == hipSuccess) e = d2h(contribution, d_nc, ms.nodes);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) rc = hip_fail(ctx, e, "module eigengenes");
+  }
+  if (rc) (void)hipStreamSynchronize(ctx->stream);  // nothing queued still uses what is freed
+  dfree(d_nc);
+  dfree(d_coh);
+  if (rc) return rc;
+  ctx->eig_n_mod = n_mod;
+  ctx->eig_gen = ctx->data_gen;
+  return NR_OK;
+}
+
+int nr_module_membership(nr_ctx* ctx, int32_t n_mod, const double* eigengenes, double* kme) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (n_mod < 1 || !kme) return fail(ctx, NR_ERR_INVALID, "n_mod < 1 or kme missing");
+  if (!ctx->ds.d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
+  if (!ctx->ds.d_data) return fail(ctx, NR_ERR_INVALID, "module membership needs a dataset with data");
+  const int64_t S = ctx->ds.n_samples, n = ctx->ds.n_nodes;
+  if (S < 3) return fail(ctx, NR_ERR_INVALID, "module membership needs at least 3 samples");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!eigengenes && (!ctx->d_eig || ctx->eig_n_mod != n_mod || ctx->eig_gen != ctx->data_gen))
+    return fail(ctx, NR_ERR_INVALID, "no eigengenes of n_mod modules from nr_module_eigengenes on this dataset");
+  NR_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->membership_ms = 0.0;
+  // Everything on the device lives for this call only and is freed on every path.
+  struct Transient {
+    double *up = nullptr, *ehat = nullptr, *kme = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    ~Transient() {
+      (void)hipStreamSynchronize(stream);
+      dfree(up);
+      dfree(ehat);
+      dfree(kme);
+      for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } t;
+  t.stream = ctx->stream;
+  const size_t e_bytes = (size_t)S * (size_t)n_mod * sizeof(double);
+  NR_HIP(ctx, hipMalloc((void**)&t.ehat, e_bytes));
+  NR_HIP(ctx, hipMalloc((void**)&t.kme, (size_t)n * (size_t)n_mod * sizeof(double)));
+  for (hipEvent_t& x : t.ev) NR_HIP(ctx, hipEventCreate(&x));
+  const double* src = ctx->d_eig;
+  if (eigengenes) {
+    NR_HIP(ctx, hipMalloc((void**)&t.up, e_bytes));
+    NR_HIP(ctx, h2d_async(t.up, eigengenes, e_bytes, ctx->stream));
+    src = t.up;
+  }
+  NR_HIP(ctx, hipEventRecord(t.ev[0], ctx->stream));
+  NR_HIP(ctx, nr::launch_eigengene_unit(src, S, n_mod, t.ehat, ctx->stream));
+  NR_HIP(ctx, nr::launch_membership(ctx->ds.d_data, S, n, t.ehat, n_mod, t.kme, ctx->stream));
+  NR_HIP(ctx, hipEventRecord(t.ev[1], ctx->stream));
+  NR_HIP(ctx, hipMemcpyAsync(kme, t.kme, (size_t)n * (size_t)n_mod * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  NR_HIP(ctx, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+  ctx->membership_ms = (double)ms;
+  return NR_OK;
+}
+
+int nr_membership_ms(nr_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return NR_ERR_INVALID;
+  *ms = ctx->membership_ms;
+  return NR_OK;
+}
+
 int nr_set_dataset_files(nr_ctx* ctx, const char* corr_path, const char* net_path, const char* data_path,
                          const char* corr_object, const char* net_object, const char* data_object,
                          int scale_data) {

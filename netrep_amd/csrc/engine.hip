@@ -759,6 +759,47 @@ int run_impl(nr_ctx* ctx, int64_t b, int64_t e, uint64_t seed, const uint32_t* p
 
 }  // namespace
 
+int upload_module_sets(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const int32_t* idx, ModuleSets& ms) {
+  ms.k_max = 0;
+  for (int m = 0; m < n_mod; ++m) {
+    const int64_t k = node_off[m + 1] - node_off[m];
+    if (k <= 0) return fail(ctx, NR_ERR_INVALID, "module with no nodes");
+    ms.k_max = std::max<int32_t>(ms.k_max, (int32_t)k);
+  }
+  ms.nodes = node_off[n_mod];
+  for (int64_t i = 0; i < ms.nodes; ++i)
+    if (idx[i] < 0 || idx[i] >= ctx->ds.n_nodes) return fail(ctx, NR_ERR_INVALID, "idx outside the dataset");
+  std::vector<int32_t>& order = ms.order;
+  order.resize(n_mod);
+  for (int m = 0; m < n_mod; ++m) order[m] = m;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    return (node_off[a + 1] - node_off[a]) > (node_off[b + 1] - node_off[b]);
+  });
+  if (int rc = upload(ctx, ms.d_off, node_off, (size_t)n_mod + 1)) return rc;
+  if (int rc = upload(ctx, ms.d_idx, idx, (size_t)ms.nodes)) return rc;
+  if (int rc = upload(ctx, ms.d_order, order.data(), order.size())) return rc;
+  ms.k_sorted.resize(n_mod);
+  for (int i = 0; i < n_mod; ++i) ms.k_sorted[i] = (int32_t)(node_off[order[i] + 1] - node_off[order[i]]);
+  return NR_OK;
+}
+
+int launch_module_profiles(nr_ctx* ctx, const ModuleSets& ms, double* d_sp, double* d_nc, double* d_coh) {
+  const int64_t S = ctx->ds.n_samples;
+  nr::ProfileParams pp{};
+  pp.data = ctx->ds.d_data;
+  pp.n_samples = S;
+  pp.ones_off = ctx->ds.n_nodes * S;
+  pp.src = make_source(ctx, nr::NR_IDX_DIRECT, 0, 0, nullptr, ms.d_idx);
+  pp.node_off = ms.d_off;
+  pp.n_perm = 1;
+  pp.sp_out = d_sp;
+  pp.nc_out = d_nc;
+  pp.coh_out = d_coh;
+  pp.queue = ctx->d_counters;
+  pp.diag = ctx->d_counters + 1;
+  return launch_profiles(ctx, pp, ms.d_order, ms.k_sorted, 1, main_lane(ctx));
+}
+
 extern "C" {
 
 int nr_device_count(int* count) {
@@ -839,6 +880,7 @@ void nr_ctx_destroy(nr_ctx* ctx) {
   dfree(ctx->obs_net_scratch);
   dfree(ctx->obs_counters);
   dfree(ctx->d_obs);
+  dfree(ctx->d_eig);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_stage2) (void)hipHostFree(ctx->h_stage2);
   if (ctx->h_scale) (void)hipHostFree(ctx->h_scale);
@@ -961,6 +1003,9 @@ int nr_release_scratch(nr_ctx* ctx) {
   ctx->obs_net_cap = 0;
   dfree(ctx->d_obs);
   ctx->obs_cap = 0;
+  dfree(ctx->d_eig);
+  ctx->eig_cap = 0;
+  ctx->eig_n_mod = 0;
   return NR_OK;
 }
 
@@ -982,6 +1027,7 @@ int nr_scratch_bytes(const nr_ctx* ctx, int64_t* bytes) {
   if (ctx->obs_scratch) t += (int64_t)ctx->obs_scratch_cap * 8;
   if (ctx->obs_net_scratch) t += (int64_t)ctx->obs_net_cap * 8;
   if (ctx->d_obs) t += (int64_t)ctx->obs_cap * 8;
+  if (ctx->d_eig) t += (int64_t)ctx->eig_cap * 8;
   *bytes = t;
   return NR_OK;
 }
@@ -1203,36 +1249,25 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
   std::lock_guard<std::mutex> lk(ctx->mu);
   NR_HIP(ctx, hipSetDevice(ctx->device));
   std::vector<int64_t> cv(n_mod + 1, 0);
-  int32_t kmax = 0;
   for (int m = 0; m < n_mod; ++m) {
     const int64_t k = node_off[m + 1] - node_off[m];
     if (k <= 0) return fail(ctx, NR_ERR_INVALID, "module with no nodes");
-    kmax = std::max<int32_t>(kmax, (int32_t)k);
     cv[m + 1] = cv[m] + k * (k - 1) / 2;
   }
-  const int64_t nodes = node_off[n_mod];
-  for (int64_t i = 0; i < nodes; ++i)
-    if (idx[i] < 0 || idx[i] >= ctx->ds.n_nodes) return fail(ctx, NR_ERR_INVALID, "idx outside the dataset");
-  std::vector<int32_t> order(n_mod);
-  for (int m = 0; m < n_mod; ++m) order[m] = m;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-    return (node_off[a + 1] - node_off[a]) > (node_off[b + 1] - node_off[b]);
-  });
-  int64_t *d_off = nullptr, *d_cv = nullptr;
-  int32_t *d_idx = nullptr, *d_order = nullptr;
+  ModuleSets ms;
+  int64_t* d_cv = nullptr;
   double *d_cvo = nullptr, *d_wd = nullptr, *d_nc = nullptr, *d_sp = nullptr, *d_coh = nullptr,
          *d_aw = nullptr;
   int rc = NR_OK;
   auto cleanup = [&]() {
-    dfree(d_off); dfree(d_cv); dfree(d_idx); dfree(d_order);
+    dfree(d_cv);
     dfree(d_cvo); dfree(d_wd); dfree(d_nc); dfree(d_sp); dfree(d_coh); dfree(d_aw);
   };
   const int64_t S = ctx->ds.n_samples;
   do {
-    if ((rc = upload(ctx, d_off, node_off, (size_t)n_mod + 1))) break;
+    if ((rc = upload_module_sets(ctx, n_mod, node_off, idx, ms))) break;
+    const int64_t nodes = ms.nodes;
     if ((rc = upload(ctx, d_cv, cv.data(), cv.size()))) break;
-    if ((rc = upload(ctx, d_idx, idx, (size_t)nodes))) break;
-    if ((rc = upload(ctx, d_order, order.data(), order.size()))) break;
     hipError_t e = hipMalloc((void**)&d_cvo, (size_t)std::max<int64_t>(cv.back(), 1) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&d_wd, (size_t)nodes * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&d_aw, (size_t)n_mod * sizeof(double));
@@ -1240,41 +1275,25 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
     if (e == hipSuccess && ctx->ds.d_data) e = hipMalloc((void**)&d_sp, (size_t)(n_mod * S) * sizeof(double));
     if (e == hipSuccess && ctx->ds.d_data) e = hipMalloc((void**)&d_coh, (size_t)n_mod * sizeof(double));
     if (e != hipSuccess) { rc = hip_fail(ctx, e, "hipMalloc module vectors"); break; }
-    nr::IndexSource src = make_source(ctx, nr::NR_IDX_DIRECT, 0, 0, nullptr, d_idx);
     nr::NetParams np{};
     np.pairs = ctx->ds.d_pairs;
     np.es = ctx->ds.pairs_es;
     np.colsum = ctx->ds.d_colsum;
     np.n_nodes = ctx->ds.n_nodes;
     np.symmetric = ctx->ds.symmetric;
-    np.src = src;
-    np.node_off = d_off;
+    np.src = make_source(ctx, nr::NR_IDX_DIRECT, 0, 0, nullptr, ms.d_idx);
+    np.node_off = ms.d_off;
     np.cv_off = d_cv;
-    np.mod_order = d_order;
+    np.mod_order = ms.d_order;
     np.n_perm = 1;
-    np.k_max = kmax;
+    np.k_max = ms.k_max;
     np.cv_out = d_cvo;
     np.wd_out = d_wd;
     np.avgw_out = d_aw;
-    std::vector<int32_t> k_sorted(n_mod);
-    for (int i = 0; i < n_mod; ++i) k_sorted[i] = (int32_t)(node_off[order[i] + 1] - node_off[order[i]]);
-    if ((rc = launch_nets(ctx, np, d_order, k_sorted, 1, main_lane(ctx)))) break;
+    if ((rc = launch_nets(ctx, np, ms.d_order, ms.k_sorted, 1, main_lane(ctx)))) break;
     e = hipSuccess;
-    if (ctx->ds.d_data && (contribution || summary || coherence)) {
-      nr::ProfileParams pp{};
-      pp.data = ctx->ds.d_data;
-      pp.n_samples = S;
-      pp.ones_off = ctx->ds.n_nodes * S;
-      pp.src = src;
-      pp.node_off = d_off;
-      pp.n_perm = 1;
-      pp.sp_out = d_sp;
-      pp.nc_out = d_nc;
-      pp.coh_out = d_coh;
-      pp.queue = ctx->d_counters;
-      pp.diag = ctx->d_counters + 1;
-      if ((rc = launch_profiles(ctx, pp, d_order, k_sorted, 1, main_lane(ctx)))) break;
-    }
+    if (ctx->ds.d_data && (contribution || summary || coherence))
+      if ((rc = launch_module_profiles(ctx, ms, d_sp, d_nc, d_coh))) break;
     auto d2h = [&](double* h, const double* d, int64_t n) {
       if (e == hipSuccess && h && n > 0)
         e = hipMemcpyAsync(h, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
@@ -1288,6 +1307,7 @@ int nr_module_vectors(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) rc = hip_fail(ctx, e, "module vectors");
   } while (0);
+  if (rc) (void)hipStreamSynchronize(ctx->stream);  // nothing queued still uses what is freed
   cleanup();
   return rc;
 }

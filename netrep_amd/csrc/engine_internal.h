@@ -52,6 +52,12 @@ struct nr_ctx {
   int64_t hclust_merges = 0;     // nr_set_hclust_merges_per_launch (0: the default, nr::kHclustMergesPerLaunch)
   double hclust_ms = 0.0;        // device time of the last call's extract and chain launches
   int64_t hclust_searches = 0, hclust_launches = 0, hclust_scratch = 0;  // of the last call (nr_hclust_info)
+  // nr_module_eigengenes / nr_module_membership (they write nothing resident)
+  double* d_eig = nullptr;       // [S x eig_n_mod] the last nr_module_eigengenes call's eigengenes (scratch)
+  size_t eig_cap = 0;
+  int32_t eig_n_mod = 0;         // 0: none
+  int64_t eig_gen = -1;          // data_gen they were computed for
+  double membership_ms = 0.0;    // device time of the last nr_module_membership call's two kernels
   int64_t table_checked = -1;    // modules_serial the Gram-table decision was made for
   int64_t data_gen = 0;          // bumped by every dataset change (reset_dataset)
   int64_t modules_gen = -1;      // data_gen the modules were validated against
@@ -202,6 +208,32 @@ static inline void sync_obs(nr_ctx* ctx) {
 // against an earlier dataset (their node indices) stop being usable:
 // check_ready demands a new nr_set_modules after any dataset change.
 void reset_dataset(nr_ctx* ctx);
+
+// engine.hip. Explicit module index sets (CSR) checked against the resident
+// dataset and uploaded, with the modules' order by decreasing size: what
+// nr_module_vectors and nr_module_eigengenes launch their kernels on. The
+// device arrays live as long as the object.
+struct ModuleSets {
+  int64_t* d_off = nullptr;
+  int32_t* d_idx = nullptr;
+  int32_t* d_order = nullptr;
+  std::vector<int32_t> order;     // the host copy behind d_order (alive while the upload may run)
+  std::vector<int32_t> k_sorted;  // module sizes in d_order's order
+  int32_t k_max = 0;
+  int64_t nodes = 0;
+  ModuleSets() = default;
+  ModuleSets(const ModuleSets&) = delete;
+  ModuleSets& operator=(const ModuleSets&) = delete;
+  ~ModuleSets() {
+    dfree(d_off);
+    dfree(d_idx);
+    dfree(d_order);
+  }
+};
+int upload_module_sets(nr_ctx* ctx, int32_t n_mod, const int64_t* node_off, const int32_t* idx, ModuleSets& ms);
+// The summary-profile launches of those sets on the context's main lane:
+// d_sp [n_mod x S], d_nc [nodes], d_coh [n_mod], all device arrays.
+int launch_module_profiles(nr_ctx* ctx, const ModuleSets& ms, double* d_sp, double* d_nc, double* d_coh);
 
 // engine.hip. Copy n doubles with up to `threads` host threads (pageable ->
 // pinned staging).

@@ -26,6 +26,7 @@
 
 #include "../../include/netrep_gpu.h"
 #include "hclust_host.h"
+#include "modmerge_host.h"
 #include "rds_reader.h"
 #include "sft_fit.h"
 
@@ -1004,6 +1005,53 @@ int live(netrep_dataset* d) {
   return NR_OK;
 }
 
+
+// The modules of a label vector as nr_module_eigengenes takes them: the
+// distinct positive labels in increasing order and their nodes in CSR form.
+struct LabelSets {
+  std::vector<int32_t> modules;
+  std::vector<int64_t> node_off;
+  std::vector<int32_t> idx;
+};
+
+int resolve_labels(const char* entry, int64_t n, const int32_t* labels, LabelSets& ls) {
+  if (!nr::module_labels_of(n, labels, ls.modules))
+    return set_err(NR_ERR_INVALID, std::string("invalid arguments to ") + entry + " (a negative label)");
+  if (ls.modules.empty())
+    return set_err(NR_ERR_INVALID, std::string("invalid arguments to ") + entry + " (no positive label)");
+  const size_t M = ls.modules.size();
+  ls.node_off.assign(M + 1, 0);
+  auto slot = [&](int32_t lab) {
+    return (size_t)(std::lower_bound(ls.modules.begin(), ls.modules.end(), lab) - ls.modules.begin());
+  };
+  for (int64_t i = 0; i < n; ++i)
+    if (labels[i] > 0) ++ls.node_off[slot(labels[i]) + 1];
+  for (size_t m = 0; m < M; ++m) ls.node_off[m + 1] += ls.node_off[m];
+  ls.idx.resize((size_t)ls.node_off[M]);
+  std::vector<int64_t> at(ls.node_off.begin(), ls.node_off.end() - 1);
+  for (int64_t i = 0; i < n; ++i)
+    if (labels[i] > 0) ls.idx[(size_t)at[slot(labels[i])]++] = (int32_t)i;
+  return NR_OK;
+}
+
+// With the handle's mutex held: the eigengenes of a label vector's modules on
+// the handle's context (they stay on the device for nr_module_membership).
+// kme_own, optional: [n] in node order, NA for label 0.
+int label_eigengenes(netrep_dataset* d, const LabelSets& ls, double* eigengenes, double* var_explained,
+                     double* kme_own) {
+  if (interrupt_requested()) return set_err(NR_ERR_CANCELLED, "interrupted");
+  nr_ctx* const c = d->ctx.get();
+  std::vector<double> nc(kme_own ? ls.idx.size() : 0);
+  const int rc = nr_module_eigengenes(c, (int32_t)ls.modules.size(), ls.node_off.data(), ls.idx.data(), eigengenes,
+                                      var_explained, kme_own ? nc.data() : nullptr);
+  if (rc) return ctx_err(rc, c);
+  if (kme_own) {
+    std::fill(kme_own, kme_own + d->n_nodes, na_real());
+    for (size_t j = 0; j < ls.idx.size(); ++j) kme_own[ls.idx[j]] = nc[j];
+  }
+  return NR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1459,6 +1507,177 @@ int netrep_DatasetHclust(netrep_dataset* d, int32_t* merge, double* height, int3
   if (rc) return ctx_err(rc, c);
   if (!nr::hclust_finish(d->n_nodes, id_lo.data(), id_hi.data(), h.data(), merge, height, order, n_repairs))
     return set_err(NR_ERR_INTERNAL, "hclust: the device returned merges that are not a binary tree");
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_EigengeneGroups(const double* eig, int64_t n_samples, int64_t n_mod, double cut_height,
+                           int32_t* group_out, double* height_out) try {
+  if (!eig || !group_out || n_samples < 2 || n_mod < 1 || (n_mod > 1 && !height_out))
+    return set_err(NR_ERR_INVALID, "invalid arguments to EigengeneGroups");
+  if (!(cut_height >= 0.0 && cut_height <= 2.0))
+    return set_err(NR_ERR_INVALID, "invalid arguments to EigengeneGroups (cut_height outside [0, 2])");
+  if (!nr::eigengene_groups(eig, n_samples, n_mod, cut_height, group_out, height_out))
+    return set_err(NR_ERR_INVALID, "invalid arguments to EigengeneGroups (a non-finite or constant eigengene)");
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+}
+
+int netrep_MergeLabels(int64_t n, const int32_t* labels_in, int64_t n_mod, const int32_t* module_labels,
+                       const int32_t* group, int32_t relabel, int32_t* labels_out) try {
+  if (n < 1 || !labels_in || n_mod < 0 || (n_mod > 0 && (!module_labels || !group)) || !labels_out)
+    return set_err(NR_ERR_INVALID, "invalid arguments to MergeLabels");
+  for (int64_t i = 0; i < n; ++i)
+    if (labels_in[i] < 0) return set_err(NR_ERR_INVALID, "invalid arguments to MergeLabels (a negative label)");
+  if (!nr::merge_labels(n, labels_in, n_mod, module_labels, group, relabel != 0, labels_out))
+    return set_err(NR_ERR_INVALID, "invalid arguments to MergeLabels (a label missing from module_labels, a module "
+                                   "label not positive or given twice, or group[m] outside 0 .. m)");
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+}
+
+int netrep_TrimModulesKME(int64_t n, const int32_t* labels_in, const double* kme_own, double min_kme_to_stay,
+                          double min_core_kme, int64_t min_core_kme_size, int64_t min_size,
+                          int32_t* labels_out) try {
+  if (n < 1 || !labels_in || !kme_own || !labels_out || std::isnan(min_kme_to_stay) || std::isnan(min_core_kme))
+    return set_err(NR_ERR_INVALID, "invalid arguments to TrimModulesKME");
+  for (int64_t i = 0; i < n; ++i)
+    if (labels_in[i] < 0) return set_err(NR_ERR_INVALID, "invalid arguments to TrimModulesKME (a negative label)");
+  nr::trim_modules_kme(n, labels_in, kme_own, min_kme_to_stay, min_core_kme, min_core_kme_size, min_size, labels_out);
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+}
+
+int netrep_DatasetModuleEigengenes(netrep_dataset* d, const int32_t* labels, int32_t* n_mod_out,
+                                   int32_t* module_labels_out, double* eigengenes, double* var_explained,
+                                   double* kme_own) try {
+  if (!d) return no_dataset("DatasetModuleEigengenes");
+  if (!labels || !eigengenes || !var_explained)
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetModuleEigengenes");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  LabelSets ls;
+  if (int rc = resolve_labels("DatasetModuleEigengenes", d->n_nodes, labels, ls)) return rc;
+  if (n_mod_out) *n_mod_out = (int32_t)ls.modules.size();
+  if (module_labels_out) std::copy(ls.modules.begin(), ls.modules.end(), module_labels_out);
+  const int rc = label_eigengenes(d, ls, eigengenes, var_explained, kme_own);
+  (void)nr_release_scratch(d->ctx.get());
+  return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetModuleMembership(netrep_dataset* d, const int32_t* labels, double* kme) try {
+  if (!d) return no_dataset("DatasetModuleMembership");
+  if (!labels || !kme) return set_err(NR_ERR_INVALID, "invalid arguments to DatasetModuleMembership");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  LabelSets ls;
+  if (int rc = resolve_labels("DatasetModuleMembership", d->n_nodes, labels, ls)) return rc;
+  nr_ctx* const c = d->ctx.get();
+  const size_t M = ls.modules.size();
+  std::vector<double> eig((size_t)d->n_samples * M), ve(M);
+  int rc = label_eigengenes(d, ls, eig.data(), ve.data(), nullptr);
+  if (!rc && interrupt_requested()) rc = set_err(NR_ERR_CANCELLED, "interrupted");
+  if (!rc) {
+    rc = nr_module_membership(c, (int32_t)M, nullptr, kme);
+    if (rc) rc = ctx_err(rc, c);
+  }
+  (void)nr_release_scratch(c);
+  return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetMergeCloseModules(netrep_dataset* d, const int32_t* labels_in, double cut_height, int32_t relabel,
+                                    int32_t* labels_out, int32_t* n_rounds_out, int32_t* n_mod_last_out,
+                                    double* eigengenes_last_out, double* heights_last_out) try {
+  if (!d) return no_dataset("DatasetMergeCloseModules");
+  if (!labels_in || !labels_out) return set_err(NR_ERR_INVALID, "invalid arguments to DatasetMergeCloseModules");
+  if (!(cut_height >= 0.0 && cut_height <= 2.0))
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetMergeCloseModules (cut_height outside [0, 2])");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  const int64_t n = d->n_nodes, S = d->n_samples;
+  std::vector<int32_t> labels(labels_in, labels_in + n), group;
+  std::vector<double> eig, ve, height;
+  LabelSets ls;
+  int32_t rounds = 0;
+  int rc = NR_OK;
+  for (;;) {
+    if ((rc = resolve_labels("DatasetMergeCloseModules", n, labels.data(), ls))) break;
+    const int64_t M = (int64_t)ls.modules.size();
+    eig.resize((size_t)(S * M));
+    ve.resize((size_t)M);
+    group.assign((size_t)M, 0);
+    height.assign((size_t)std::max<int64_t>(M - 1, 0), 0.0);
+    if ((rc = label_eigengenes(d, ls, eig.data(), ve.data(), nullptr))) break;
+    if (M == 1) break;
+    if (!nr::eigengene_groups(eig.data(), S, M, cut_height, group.data(), height.data())) {
+      rc = set_err(NR_ERR_NONFINITE, "mergeCloseModules: a non-finite or constant eigengene");
+      break;
+    }
+    bool merged = false;
+    for (int64_t m = 0; m < M; ++m) merged = merged || group[(size_t)m] != (int32_t)m;
+    if (!merged) break;
+    nr::merge_labels(n, labels.data(), M, ls.modules.data(), group.data(), false, labels.data());
+    ++rounds;
+  }
+  (void)nr_release_scratch(d->ctx.get());
+  if (rc) return rc;
+  // ls, eig and height are the last round's: the final modules in increasing label order
+  const size_t M = ls.modules.size();
+  std::vector<int32_t> column_of(M);  // source column of each output column
+  for (size_t m = 0; m < M; ++m) column_of[m] = (int32_t)m;
+  if (relabel) {
+    std::vector<int32_t> old_of_new;
+    nr::relabel_by_size(n, labels.data(), labels.data(), &old_of_new);
+    for (size_t m = 0; m < M; ++m)
+      column_of[m] =
+          (int32_t)(std::lower_bound(ls.modules.begin(), ls.modules.end(), old_of_new[m]) - ls.modules.begin());
+  }
+  std::copy(labels.begin(), labels.end(), labels_out);
+  if (n_rounds_out) *n_rounds_out = rounds;
+  if (n_mod_last_out) *n_mod_last_out = (int32_t)M;
+  if (eigengenes_last_out)
+    for (size_t m = 0; m < M; ++m)
+      std::copy(eig.begin() + (size_t)column_of[m] * (size_t)S, eig.begin() + ((size_t)column_of[m] + 1) * (size_t)S,
+                eigengenes_last_out + m * (size_t)S);
+  if (heights_last_out) std::copy(height.begin(), height.end(), heights_last_out);
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetTrimModules(netrep_dataset* d, const int32_t* labels_in, double min_kme_to_stay,
+                              double min_core_kme, int64_t min_core_kme_size, int64_t min_size,
+                              int32_t* labels_out) try {
+  if (!d) return no_dataset("DatasetTrimModules");
+  if (!labels_in || !labels_out || std::isnan(min_kme_to_stay) || std::isnan(min_core_kme))
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetTrimModules");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  LabelSets ls;
+  if (int rc = resolve_labels("DatasetTrimModules", d->n_nodes, labels_in, ls)) return rc;
+  const size_t M = ls.modules.size();
+  std::vector<double> eig((size_t)d->n_samples * M), ve(M), own((size_t)d->n_nodes);
+  const int rc = label_eigengenes(d, ls, eig.data(), ve.data(), own.data());
+  (void)nr_release_scratch(d->ctx.get());
+  if (rc) return rc;
+  nr::trim_modules_kme(d->n_nodes, labels_in, own.data(), min_kme_to_stay, min_core_kme, min_core_kme_size, min_size,
+                       labels_out);
   return NR_OK;
 } catch (const std::bad_alloc&) {
   return set_err(NR_ERR_OOM, "host memory allocation failed");

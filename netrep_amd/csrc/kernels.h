@@ -259,6 +259,27 @@ size_t hclust_state_bytes(int64_t n);
 HclustParams hclust_params(int64_t n, double* D, void* state);
 hipError_t launch_hclust_extract(const double2* pairs, int es, const HclustParams& P, hipStream_t st);
 hipError_t launch_hclust_chain(const HclustParams& P, hipStream_t st);
+// Module membership (membership.hip, nr_module_membership): ehat = the centred,
+// unit-norm columns of eig (S x M, column-major); kme [n x M, column-major] =
+// the correlation of every column of the node-major data block with every
+// column of ehat. A workgroup holds kMembershipNodes centred columns in LDS
+// while ehat passes by in tiles of 16 rm eigengenes; membership_tile, a pure
+// function of S, gives rm (eigengenes per thread), the sample chunk, the LDS
+// row stride and the bytes: the largest rm of 4, 2, 1 whose
+// (16 + 16 rm) (S | 1) doubles fit kMembershipLds with the whole column
+// resident (S <= 229, 383, 575); beyond that rm = 1 and columns and tile are
+// both walked in chunks of kMembershipChunk samples.
+constexpr int kMembershipNodes = 16;
+constexpr size_t kMembershipLds = 144 * 1024;
+constexpr int kMembershipChunk = 512;
+struct MembershipTile {
+  int rm, chunk, pad;
+  size_t lds;
+};
+MembershipTile membership_tile(int64_t S);
+hipError_t launch_eigengene_unit(const double* eig, int64_t S, int M, double* ehat, hipStream_t st);
+hipError_t launch_membership(const double* data, int64_t S, int64_t n, const double* ehat, int M, double* kme,
+                             hipStream_t st);
 // corr[e], net[e] (either may be NULL) = elements [first, first + len) of a
 // pair array in layout es (1, or 2: the Gram table).
 hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,

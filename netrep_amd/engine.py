@@ -397,6 +397,55 @@ class Engine:
             out.update(contribution=nc, summary=sp.reshape(n_mod, self.n_samples), coherence=coh)
         return out
 
+    def module_eigengenes(self, node_off, idx):
+        """The eigengenes of explicit index sets (CSR) on the resident data
+        (nr_module_eigengenes: the summary-profile kernels alone): a dict of
+        ``eigengenes`` (S x M, Fortran order), ``varExplained`` (M) and
+        ``kME`` (each node's correlation with its own module's eigengene, CSR
+        order). The eigengenes also stay on the device for
+        ``module_membership()``."""
+        node_off = np.ascontiguousarray(node_off, dtype=np.int64)
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        n_mod = node_off.size - 1
+        eig = np.empty((self.n_samples, max(n_mod, 0)), dtype=np.float64, order="F")
+        ve = np.empty(max(n_mod, 0))
+        nc = np.empty(int(node_off[-1]))
+        self._check(self._lib.nr_module_eigengenes(self._h, int(n_mod), _ptr(node_off, C.c_int64),
+                                                   _ptr(idx, C.c_int32), _ptr(eig), _ptr(ve), _ptr(nc)))
+        return {"eigengenes": eig, "varExplained": ve, "kME": nc}
+
+    def module_membership(self, n_mod: int, eigengenes=None) -> np.ndarray:
+        """kME of every node of the resident data with ``n_mod`` eigengenes
+        (nr_module_membership): an ``(n_nodes, n_mod)`` Fortran-ordered array.
+        ``eigengenes`` None: those of the last ``module_eigengenes`` call,
+        still on the device; else an ``(S, n_mod)`` host array, uploaded."""
+        e = None
+        if eigengenes is not None:
+            e = _f64(eigengenes)
+            if e.shape != (self.n_samples, int(n_mod)):
+                raise ValueError("eigengenes must be an (n_samples, n_mod) matrix")
+        n, _s = self.shape()
+        kme = np.empty((n, int(n_mod)), dtype=np.float64, order="F")
+        self._check(self._lib.nr_module_membership(self._h, int(n_mod), _ptr(e), _ptr(kme)))
+        return kme
+
+    def membership_ms(self) -> float:
+        """Device time in ms of the two kernels of this engine's last
+        ``module_membership`` call (nr_membership_ms)."""
+        ms = C.c_double()
+        self._check(self._lib.nr_membership_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def release_scratch(self):
+        """Free the per-batch work buffers (nr_release_scratch)."""
+        self._check(self._lib.nr_release_scratch(self._h))
+
+    def scratch_bytes(self) -> int:
+        """Device bytes of per-batch work buffers held (nr_scratch_bytes)."""
+        b = C.c_int64()
+        self._check(self._lib.nr_scratch_bytes(self._h, C.byref(b)))
+        return int(b.value)
+
     def scale(self, data) -> np.ndarray:
         data = _f64(data)
         out = np.empty_like(data, order="F")
