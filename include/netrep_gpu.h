@@ -310,6 +310,43 @@ int nr_module_membership(nr_ctx* ctx, int32_t n_mod, const double* eigengenes, d
 /* Device time in ms (HIP events) of the two kernels of the context's last
  * nr_module_membership call; 0 before the first. */
 int nr_membership_ms(nr_ctx* ctx, double* ms);
+/* Module connectivity of every node of the resident network: the network-side
+ * counterpart of nr_module_membership. slot [n_nodes]: node j's module index
+ * 0 .. n_mod - 1, or -1 for an unassigned node. With net the resident network
+ * (adjacency or TOM),
+ *   k_mod[i, m] = sum over j != i with slot[j] == m of |net[j, i]|,
+ *   k_total[i]  = sum over all j != i of |net[j, i]|, unassigned nodes included.
+ * k_mod [n_nodes x n_mod, column-major]; k_total [n_nodes], may be NULL.
+ * The absolute value is what NetRep's weighted degree takes
+ * (src/netStats.cpp:135); a from-data network is non-negative already, so
+ * there it changes no bit, and a dataset set from host matrices with negative
+ * weights is summed by magnitude, as nr_module_vectors' degree is.
+ * The summation order is part of the contract:
+ *   - each sum is split into 64 partials; partial l adds the participating
+ *     rows j = l (mod 64) in increasing j, starting from +0.0;
+ *   - the partials are combined by p[l] += p[l + off] for l < off, with
+ *     off = 32, 16, 8, 4, 2, 1; the result is p[0];
+ *   - a row that does not take part (the diagonal, another module's row) adds
+ *     nothing, which for |net| >= 0 is the same as adding +0.0;
+ *   - only additions occur, none fused, and there are no atomics.
+ * So a cell's bits depend on (net, slot) alone: not on n_mod, on the module
+ * tile, on the pair layout or on the device. k_total is not derived from the
+ * module cells.
+ * The network is read in either pair layout, once per module tile: n_mod
+ * modules take ceil(n_mod / 64) passes, the tile being n_mod split evenly
+ * among them. Device scratch for the call: 4 n + 8 n (n_mod + 1) bytes (slots,
+ * table, k_total), freed before the call returns on every path; a failed
+ * allocation returns NR_ERR_OOM naming the bytes. Nothing resident is
+ * written and nr_scratch_bytes is unchanged. Any n_nodes >= 1 and n_mod >= 1.
+ * NR_ERR_INVALID: n_mod < 1, slot or k_mod missing, no dataset, a slot
+ * outside -1 .. n_mod - 1. */
+int nr_module_connectivity(nr_ctx* ctx, int32_t n_mod, const int32_t* slot, double* k_total, double* k_mod);
+/* Device time in ms (HIP events) of the kernels of the context's last
+ * nr_module_connectivity call; 0 before the first. */
+int nr_connectivity_ms(nr_ctx* ctx, double* ms);
+/* Test knob: modules per pass of later nr_module_connectivity calls on this
+ * context, 1 .. 64; 0 restores the default. It changes no result. */
+int nr_set_connectivity_module_tile(nr_ctx* ctx, int32_t tile);
 /* The resident corr and net (n_nodes x n_nodes each, column-major) to host
  * arrays; either may be NULL. Works for a dataset made by any of the
  * set-dataset calls, before or after the Gram table is built: the pairs are
@@ -921,7 +958,8 @@ int netrep_MergeLabels(int64_t n, const int32_t* labels_in, int64_t n_mod, const
  * n < 1, a negative label, a NaN threshold. */
 int netrep_TrimModulesKME(int64_t n, const int32_t* labels_in, const double* kme_own, double min_kme_to_stay,
                           double min_core_kme, int64_t min_core_kme_size, int64_t min_size, int32_t* labels_out);
-/* On the handle. Common to the four: labels [n_nodes] as above;
+/* On the handle. Common to the netrep_Dataset* entries below, down to
+ * netrep_DatasetTrimModules: labels [n_nodes] as above;
  * NR_ERR_INVALID with a text naming it for a NULL argument, a negative
  * label, or a label vector with no positive label; the interrupt hook is
  * polled before every device call (NR_ERR_CANCELLED); the handle's dataset
@@ -941,6 +979,40 @@ int netrep_DatasetModuleEigengenes(netrep_dataset* d, const int32_t* labels, int
  * nr_module_membership on the context's copy of them. kme [n_nodes x M,
  * column-major]. */
 int netrep_DatasetModuleMembership(netrep_dataset* d, const int32_t* labels, double* kme);
+/* The eigengene tree itself (a pure host function): the tree that
+ * netrep_EigengeneGroups cuts -- the same cor(E), the same "globally closest
+ * pair, ties to the lowest (lower, higher) pair" rule, clusters indexed by
+ * their lowest column -- with the linkage chosen: NR_LINKAGE_AVERAGE (the
+ * bits of netrep_EigengeneGroups' heights) or NR_LINKAGE_COMPLETE,
+ * d(k, a u b) = max(d(k, a), d(k, b)), R's hclust default. It emits the
+ * merges as nr_hclust_average does, in discovery order, for
+ * netrep_HclustFinish: step t = 0 .. M - 2 gives id_lo[t], id_hi[t] (the ids
+ * of the clusters with the lower and the higher lowest column: 0 .. M - 1
+ * are columns, M + u is the cluster of step u) and height[t]. M = 1 writes
+ * nothing. NR_ERR_INVALID: a NULL pointer (the outputs may be NULL when
+ * M = 1), S < 2, M < 1, an unknown linkage, a non-finite or constant column. */
+#define NR_LINKAGE_AVERAGE 0
+#define NR_LINKAGE_COMPLETE 1
+int netrep_EigengeneTree(const double* eig, int64_t n_samples, int64_t n_mod, int32_t linkage, int32_t* id_lo,
+                         int32_t* id_hi, double* height);
+/* Connectivity by module, the network-side counterpart of the kME table.
+ * slot[j] is node j's module index 0 .. M - 1 among the distinct positive
+ * labels in increasing order, or -1 for label 0; the table and the summation
+ * order are nr_module_connectivity's (the definition is there).
+ * netrep_DatasetModuleConnectivity: k_total [n_nodes] (optional) and k_mod
+ * [n_nodes x M, column-major] of the handle's network; conventions as the
+ * other label entries on the handle. */
+int netrep_DatasetModuleConnectivity(netrep_dataset* d, const int32_t* labels, double* k_total, double* k_mod);
+/* WGCNA's intramodularConnectivity from that table (a pure host function;
+ * k_total [n], k_mod [n x M, column-major] as above):
+ *   k_within[i] = k_mod[i, slot[i]], k_out = k_total - k_within,
+ *   k_diff = k_within - k_out, each one rounding; NaN all three for label 0.
+ * NR_ERR_INVALID: a NULL pointer, n < 1, a negative label, no positive label. */
+int netrep_IntramodularConnectivity(int64_t n, const int32_t* labels, const double* k_total, const double* k_mod,
+                                    double* k_within, double* k_out, double* k_diff);
+/* Both on the handle: the four vectors [n_nodes] of its network. */
+int netrep_DatasetIntramodularConnectivity(netrep_dataset* d, const int32_t* labels, double* k_total,
+                                           double* k_within, double* k_out, double* k_diff);
 /* WGCNA's mergeCloseModules with iterate = TRUE. A round computes the
  * eigengenes of the current labels, builds their tree, cuts it at cut_height
  * (netrep_EigengeneGroups) and merges (netrep_MergeLabels, no relabelling);

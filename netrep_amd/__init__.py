@@ -14,7 +14,7 @@ from .api import (CheckFinite, IntermediateProperties, IntermediatePropertiesNoD
                   PermutationProcedureFromData, BuildNetwork, PickSoftThreshold, ScaleFreeFit,
                   FromDataDataset, IntermediatePropertiesFromData, NetPropsFromData, modulePreservationFromData,
                   DetectModulesFromData, cutreeStatic, hclustFinish, eigengeneGroups, mergeLabels, trimModulesKME,
-                  read_rds_matrix, Scale, STATNAMES, STATNAMES_NODATA,
+                  eigengeneTree, intramodularConnectivity, read_rds_matrix, Scale, STATNAMES, STATNAMES_NODATA,
                   set_interrupt_hook)
 from .engine import Engine, device_count, prp_table  # noqa: F401
 
@@ -26,4 +26,5 @@ __all__ = ["CheckFinite", "IntermediateProperties", "IntermediatePropertiesNoDat
            "PermutationProcedureFromData", "BuildNetwork", "PickSoftThreshold", "ScaleFreeFit",
            "FromDataDataset", "IntermediatePropertiesFromData", "NetPropsFromData",
            "modulePreservationFromData", "DetectModulesFromData", "cutreeStatic", "hclustFinish",
-           "eigengeneGroups", "mergeLabels", "trimModulesKME"]
+           "eigengeneGroups", "mergeLabels", "trimModulesKME", "eigengeneTree",
+           "intramodularConnectivity"]

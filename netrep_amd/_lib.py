@@ -166,6 +166,13 @@ SIGNATURES = {
     "nr_module_eigengenes": (_int, [_p, _i32, _i64p, _i32p, _dp, _dp, _dp]),
     "nr_module_membership": (_int, [_p, _i32, _dp, _dp]),
     "nr_membership_ms": (_int, [_p, C.POINTER(C.c_double)]),
+    "nr_module_connectivity": (_int, [_p, _i32, _i32p, _dp, _dp]),
+    "nr_connectivity_ms": (_int, [_p, C.POINTER(C.c_double)]),
+    "nr_set_connectivity_module_tile": (_int, [_p, _i32]),
+    "netrep_EigengeneTree": (_int, [_dp, _i64, _i64, _i32, _i32p, _i32p, _dp]),
+    "netrep_IntramodularConnectivity": (_int, [_i64, _i32p, _dp, _dp, _dp, _dp, _dp]),
+    "netrep_DatasetModuleConnectivity": (_int, [_p, _i32p, _dp, _dp]),
+    "netrep_DatasetIntramodularConnectivity": (_int, [_p, _i32p, _dp, _dp, _dp, _dp]),
     "netrep_EigengeneGroups": (_int, [_dp, _i64, _i64, C.c_double, _i32p, _dp]),
     "netrep_MergeLabels": (_int, [_i64, _i32p, _i64, _i32p, _i32p, _i32, _i32p]),
     "netrep_TrimModulesKME": (_int, [_i64, _i32p, _dp, C.c_double, C.c_double, _i64, _i64, _i32p]),

@@ -866,6 +866,76 @@ class FromDataDataset:
                                                        int(minSize), _i32ptr(out)))
         return out
 
+    # -- connectivity by module: the table, hub nodes, node and sample order -
+    def module_connectivity(self, labels):
+        """The module-connectivity table, the network-side counterpart of
+        ``module_membership``, computed on the GPU from the resident network
+        (netrep_DatasetModuleConnectivity): ``(kMod, kTotal)``. ``kMod`` has n
+        rows named by node and columns ``"k<label>"``: the summed weight of
+        the node's edges into each module of ``labels`` (itself excluded);
+        ``kTotal`` (n) the same over every other node, unassigned ones
+        included."""
+        h = self._handle()
+        lab = self._labels(labels)
+        mods = np.unique(lab[lab > 0])
+        k_mod = np.zeros((self.n_nodes, max(int(mods.size), 1)), order="F")
+        k_total = np.zeros(self.n_nodes)
+        L.check_api(L.load().netrep_DatasetModuleConnectivity(h, _i32ptr(lab), _dptr(k_total), _dptr(k_mod)))
+        return RMatrix(k_mod, list(self.node_names), [f"k{int(m)}" for m in mods]), k_total
+
+    def intramodular_connectivity(self, labels) -> dict:
+        """WGCNA's ``intramodularConnectivity`` on the handle's network
+        (netrep_DatasetIntramodularConnectivity): ``kTotal``, ``kWithin`` (the
+        node's connectivity to its own module), ``kOut = kTotal - kWithin``
+        and ``kDiff = kWithin - kOut``, each of length n, the last three NaN
+        for label 0; ``modules`` the distinct positive labels."""
+        h = self._handle()
+        lab = self._labels(labels)
+        out = {k: np.zeros(self.n_nodes) for k in ("kTotal", "kWithin", "kOut", "kDiff")}
+        L.check_api(L.load().netrep_DatasetIntramodularConnectivity(h, _i32ptr(lab), *(_dptr(v) for v in out.values())))
+        out["modules"] = np.unique(lab[lab > 0]).astype(np.int32)
+        return out
+
+    def hub_nodes(self, labels) -> dict:
+        """Per module the node with the largest ``kWithin``, ties to the
+        lowest node index: ``{label: node name}``."""
+        lab = self._labels(labels)
+        k = self.intramodular_connectivity(lab)
+        hubs = {}
+        for m in k["modules"]:
+            idx = np.flatnonzero(lab == m)
+            hubs[int(m)] = self.node_names[int(idx[int(np.argmax(k["kWithin"][idx]))])]
+        return hubs
+
+    def node_order(self, labels, orderModules: bool = True) -> dict:
+        """NetRep's ``nodeOrder`` for this one dataset (R/orderNodes.R, mean =
+        FALSE, every node present). Modules stand in the leaf order of the
+        complete-linkage tree of their eigengenes on 1 - cor
+        (netrep_EigengeneTree, netrep_HclustFinish: R's ``hclust`` default);
+        with one module or ``orderModules=False`` in increasing label order.
+        Within a module the nodes stand by decreasing ``kWithin``, ties in
+        node order. ``nodes``: the node names flattened (simplify = TRUE);
+        ``modules``: ``{label: [node names]}`` in module order."""
+        lab = self._labels(labels)
+        k = self.intramodular_connectivity(lab)
+        mods = [int(m) for m in k["modules"]]
+        if orderModules and len(mods) > 1:
+            id_lo, id_hi, height = eigengeneTree(self.module_eigengenes(lab)["eigengenes"], "complete")
+            _merge, _h, order, _r = hclustFinish(len(mods), id_lo, id_hi, height)
+            mods = [mods[int(o) - 1] for o in order]
+        by_module = {}
+        for m in mods:
+            idx = np.flatnonzero(lab == m)
+            by_module[m] = [self.node_names[int(i)] for i in idx[np.argsort(-k["kWithin"][idx], kind="stable")]]
+        return {"nodes": [nm for m in mods for nm in by_module[m]], "modules": by_module}
+
+    def sample_order(self, labels) -> dict:
+        """NetRep's ``sampleOrder`` (R/orderSamples.R): per module the
+        0-based sample indices by decreasing eigengene value, ties in sample
+        order: ``{label: indices}``, from ``module_eigengenes``."""
+        e = self.module_eigengenes(labels)
+        return {int(m): np.argsort(-e["eigengenes"][:, j], kind="stable") for j, m in enumerate(e["modules"])}
+
 
 def _i32ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
@@ -884,6 +954,46 @@ def eigengeneGroups(eigengenes, cutHeight: float):
     heights = np.zeros(max(m - 1, 1))
     L.check_api(L.load().netrep_EigengeneGroups(_dptr(e), s, m, float(cutHeight), _i32ptr(group), _dptr(heights)))
     return group[:m], heights[:max(m - 1, 0)]
+
+
+LINKAGES = {"average": 0, "complete": 1}
+
+
+def eigengeneTree(eigengenes, linkage: str = "complete"):
+    """The eigengene tree (netrep_EigengeneTree; a pure host function) of an
+    (S x M) eigengene matrix on 1 - cor with ``linkage`` "average" or
+    "complete": ``(id_lo, id_hi, height)``, M - 1 merges in discovery order
+    as ``hclustFinish`` takes them."""
+    e = np.asfortranarray(np.asarray(eigengenes, dtype=np.float64))
+    if e.ndim != 2:
+        raise L.NetRepError(L.NR_ERR_INVALID, "eigengenes must be a samples x modules matrix")
+    if linkage not in LINKAGES:
+        raise L.NetRepError(L.NR_ERR_INVALID, f"unknown linkage {linkage!r}: one of 'average', 'complete'")
+    s, m = e.shape
+    id_lo = np.zeros(max(m - 1, 1), dtype=np.int32)
+    id_hi = np.zeros(max(m - 1, 1), dtype=np.int32)
+    height = np.zeros(max(m - 1, 1))
+    L.check_api(L.load().netrep_EigengeneTree(_dptr(e), s, m, LINKAGES[linkage], _i32ptr(id_lo), _i32ptr(id_hi),
+                                              _dptr(height)))
+    k = max(m - 1, 0)
+    return id_lo[:k], id_hi[:k], height[:k]
+
+
+def intramodularConnectivity(labels, kTotal, kMod) -> dict:
+    """``kWithin``, ``kOut`` and ``kDiff`` from a module-connectivity table
+    (netrep_IntramodularConnectivity; a pure host function): ``kMod`` (n x M,
+    its columns the distinct positive labels in increasing order) and
+    ``kTotal`` (n) as ``FromDataDataset.module_connectivity`` returns them."""
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    tot = np.ascontiguousarray(kTotal, dtype=np.float64)
+    table = np.asfortranarray(np.asarray(kMod, dtype=np.float64))
+    m = int(np.unique(lab[lab > 0]).size) if lab.ndim == 1 else 0
+    if lab.ndim != 1 or tot.shape != lab.shape or table.shape != (lab.size, max(m, 1)):
+        raise L.NetRepError(L.NR_ERR_INVALID, "labels and kTotal must be vectors of one length n, kMod n x modules")
+    out = {k: np.zeros(max(lab.size, 1)) for k in ("kWithin", "kOut", "kDiff")}
+    L.check_api(L.load().netrep_IntramodularConnectivity(lab.size, _i32ptr(lab), _dptr(tot), _dptr(table),
+                                                         *(_dptr(v) for v in out.values())))
+    return {k: v[:lab.size] for k, v in out.items()}
 
 
 def mergeLabels(labels, moduleLabels, group, relabel: bool = False) -> np.ndarray:

@@ -768,6 +768,78 @@ int nr_membership_ms(nr_ctx* ctx, double* ms) {
   return NR_OK;
 }
 
+int nr_module_connectivity(nr_ctx* ctx, int32_t n_mod, const int32_t* slot, double* k_total, double* k_mod) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (n_mod < 1 || !slot || !k_mod) return fail(ctx, NR_ERR_INVALID, "n_mod < 1, or slot or k_mod missing");
+  if (!ctx->ds.d_pairs) return fail(ctx, NR_ERR_INVALID, "no dataset");
+  const int64_t n = ctx->ds.n_nodes;
+  for (int64_t j = 0; j < n; ++j)
+    if (slot[j] < -1 || slot[j] >= n_mod)
+      return fail(ctx, NR_ERR_INVALID, "slot[" + std::to_string(j) + "] = " + std::to_string(slot[j]) +
+                                           " is outside -1 .. n_mod - 1");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  NR_HIP(ctx, hipSetDevice(ctx->device));
+  // the table build replaces d_pairs between launches only; wait for both lanes
+  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (ctx->obs_stream) NR_HIP(ctx, hipStreamSynchronize(ctx->obs_stream));
+  ctx->connectivity_ms = 0.0;
+  // Everything on the device lives for this call only and is freed on every path.
+  struct Transient {
+    char* buf = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    ~Transient() {
+      (void)hipStreamSynchronize(stream);  // nothing queued still uses what is freed
+      dfree(buf);
+      for (hipEvent_t x : ev)
+        if (x) (void)hipEventDestroy(x);
+    }
+  } t;
+  t.stream = ctx->stream;
+  // k_mod [n x n_mod] | k_total [n] | slot [n]
+  const size_t cells = (size_t)n * ((size_t)n_mod + 1);
+  const size_t bytes = cells * sizeof(double) + (size_t)n * sizeof(int32_t);
+  if (hipMalloc((void**)&t.buf, bytes) != hipSuccess) {
+    t.buf = nullptr;
+    (void)hipGetLastError();
+    return fail(ctx, NR_ERR_OOM, "module connectivity: allocation of the " + std::to_string(bytes) + "-byte (" +
+                                     std::to_string(bytes >> 20) + " MiB) scratch failed (4 n + 8 n (n_mod + 1) bytes)");
+  }
+  double* const d_mod = reinterpret_cast<double*>(t.buf);
+  double* const d_tot = d_mod + (size_t)n * (size_t)n_mod;
+  int32_t* const d_slot = reinterpret_cast<int32_t*>(d_mod + cells);
+  for (hipEvent_t& x : t.ev) NR_HIP(ctx, hipEventCreate(&x));
+  NR_HIP(ctx, h2d_async(d_slot, slot, (size_t)n * sizeof(int32_t), ctx->stream));
+  NR_HIP(ctx, hipEventRecord(t.ev[0], ctx->stream));
+  NR_HIP(ctx, nr::launch_connectivity(ctx->ds.d_pairs, ctx->ds.pairs_es, n, d_slot, n_mod, ctx->connectivity_tile,
+                                      d_tot, d_mod, ctx->stream));
+  NR_HIP(ctx, hipEventRecord(t.ev[1], ctx->stream));
+  NR_HIP(ctx, hipMemcpyAsync(k_mod, d_mod, (size_t)n * (size_t)n_mod * sizeof(double), hipMemcpyDeviceToHost,
+                             ctx->stream));
+  if (k_total)
+    NR_HIP(ctx, hipMemcpyAsync(k_total, d_tot, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  NR_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  NR_HIP(ctx, hipEventElapsedTime(&ms, t.ev[0], t.ev[1]));
+  ctx->connectivity_ms = (double)ms;
+  return NR_OK;
+}
+
+int nr_connectivity_ms(nr_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return NR_ERR_INVALID;
+  *ms = ctx->connectivity_ms;
+  return NR_OK;
+}
+
+int nr_set_connectivity_module_tile(nr_ctx* ctx, int32_t tile) {
+  if (!ctx) return NR_ERR_INVALID;
+  if (tile < 0 || tile > nr::kConnectivityTileMax)
+    return fail(ctx, NR_ERR_INVALID,
+                "module tile must be 0 (the default) .. " + std::to_string(nr::kConnectivityTileMax));
+  ctx->connectivity_tile = tile;
+  return NR_OK;
+}
+
 int nr_set_dataset_files(nr_ctx* ctx, const char* corr_path, const char* net_path, const char* data_path,
                          const char* corr_object, const char* net_object, const char* data_object,
                          int scale_data) {

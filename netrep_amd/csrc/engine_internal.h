@@ -58,7 +58,10 @@ struct nr_ctx {
   int32_t eig_n_mod = 0;         // 0: none
   int64_t eig_gen = -1;          // data_gen they were computed for
   double membership_ms = 0.0;    // device time of the last nr_module_membership call's two kernels
-  int64_t table_checked = -1;    // modules_serial the Gram-table decision was made for
+  // nr_module_connectivity (it reads the resident net and writes nothing resident)
+  double connectivity_ms = 0.0;  // device time of the last call's kernels
+  int32_t connectivity_tile = 0; // nr_set_connectivity_module_tile (0: the default, nr::connectivity_tile(M))
+  int64_t table_checked = -1;   // modules_serial the Gram-table decision was made for
   int64_t data_gen = 0;          // bumped by every dataset change (reset_dataset)
   int64_t modules_gen = -1;      // data_gen the modules were validated against
   int64_t modules_serial = 0;    // bumped by every nr_set_modules

@@ -1052,6 +1052,29 @@ int label_eigengenes(netrep_dataset* d, const LabelSets& ls, double* eigengenes,
   return NR_OK;
 }
 
+// slot[j]: node j's module index in ls.modules, -1 for label 0.
+std::vector<int32_t> slots_of(int64_t n, const int32_t* labels, const LabelSets& ls) {
+  std::vector<int32_t> slot((size_t)n, -1);
+  for (int64_t j = 0; j < n; ++j)
+    if (labels[j] > 0)
+      slot[(size_t)j] =
+          (int32_t)(std::lower_bound(ls.modules.begin(), ls.modules.end(), labels[j]) - ls.modules.begin());
+  return slot;
+}
+
+// With the handle's mutex held: nr_module_connectivity of a label vector's
+// modules on the handle's context.
+int label_connectivity(netrep_dataset* d, const int32_t* labels, const LabelSets& ls, double* k_total,
+                       double* k_mod) {
+  if (interrupt_requested()) return set_err(NR_ERR_CANCELLED, "interrupted");
+  nr_ctx* const c = d->ctx.get();
+  const std::vector<int32_t> slot = slots_of(d->n_nodes, labels, ls);
+  int rc = nr_module_connectivity(c, (int32_t)ls.modules.size(), slot.data(), k_total, k_mod);
+  if (rc) rc = ctx_err(rc, c);
+  (void)nr_release_scratch(c);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1593,6 +1616,69 @@ int netrep_DatasetModuleMembership(netrep_dataset* d, const int32_t* labels, dou
   }
   (void)nr_release_scratch(c);
   return rc;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_EigengeneTree(const double* eig, int64_t n_samples, int64_t n_mod, int32_t linkage, int32_t* id_lo,
+                         int32_t* id_hi, double* height) try {
+  if (!eig || n_samples < 2 || n_mod < 1 || (n_mod > 1 && (!id_lo || !id_hi || !height)))
+    return set_err(NR_ERR_INVALID, "invalid arguments to EigengeneTree");
+  if (linkage != NR_LINKAGE_AVERAGE && linkage != NR_LINKAGE_COMPLETE)
+    return set_err(NR_ERR_INVALID, "invalid arguments to EigengeneTree (linkage is neither average nor complete)");
+  if (!nr::eigengene_tree(eig, n_samples, n_mod,
+                          linkage == NR_LINKAGE_COMPLETE ? nr::kLinkageComplete : nr::kLinkageAverage, id_lo, id_hi,
+                          height))
+    return set_err(NR_ERR_INVALID, "invalid arguments to EigengeneTree (a non-finite or constant eigengene)");
+  nr::tree_slots_to_ids(n_mod, id_lo, id_hi, id_lo, id_hi);
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+}
+
+int netrep_IntramodularConnectivity(int64_t n, const int32_t* labels, const double* k_total, const double* k_mod,
+                                    double* k_within, double* k_out, double* k_diff) try {
+  if (n < 1 || !labels || !k_total || !k_mod || !k_within || !k_out || !k_diff)
+    return set_err(NR_ERR_INVALID, "invalid arguments to IntramodularConnectivity");
+  LabelSets ls;
+  if (int rc = resolve_labels("IntramodularConnectivity", n, labels, ls)) return rc;
+  const std::vector<int32_t> slot = slots_of(n, labels, ls);
+  nr::intramodular_connectivity(n, slot.data(), k_total, k_mod, k_within, k_out, k_diff);
+  return NR_OK;
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+}
+
+int netrep_DatasetModuleConnectivity(netrep_dataset* d, const int32_t* labels, double* k_total, double* k_mod) try {
+  if (!d) return no_dataset("DatasetModuleConnectivity");
+  if (!labels || !k_mod) return set_err(NR_ERR_INVALID, "invalid arguments to DatasetModuleConnectivity");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  LabelSets ls;
+  if (int rc = resolve_labels("DatasetModuleConnectivity", d->n_nodes, labels, ls)) return rc;
+  return label_connectivity(d, labels, ls, k_total, k_mod);
+} catch (const std::bad_alloc&) {
+  return set_err(NR_ERR_OOM, "host memory allocation failed");
+} catch (const std::exception& e) {
+  return set_err(NR_ERR_INVALID, std::string("internal error: ") + e.what());
+}
+
+int netrep_DatasetIntramodularConnectivity(netrep_dataset* d, const int32_t* labels, double* k_total,
+                                           double* k_within, double* k_out, double* k_diff) try {
+  if (!d) return no_dataset("DatasetIntramodularConnectivity");
+  if (!labels || !k_total || !k_within || !k_out || !k_diff)
+    return set_err(NR_ERR_INVALID, "invalid arguments to DatasetIntramodularConnectivity");
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (int rc = live(d)) return rc;
+  LabelSets ls;
+  if (int rc = resolve_labels("DatasetIntramodularConnectivity", d->n_nodes, labels, ls)) return rc;
+  std::vector<double> k_mod((size_t)d->n_nodes * ls.modules.size());
+  if (int rc = label_connectivity(d, labels, ls, k_total, k_mod.data())) return rc;
+  const std::vector<int32_t> slot = slots_of(d->n_nodes, labels, ls);
+  nr::intramodular_connectivity(d->n_nodes, slot.data(), k_total, k_mod.data(), k_within, k_out, k_diff);
+  return NR_OK;
 } catch (const std::bad_alloc&) {
   return set_err(NR_ERR_OOM, "host memory allocation failed");
 } catch (const std::exception& e) {

@@ -280,6 +280,19 @@ MembershipTile membership_tile(int64_t S);
 hipError_t launch_eigengene_unit(const double* eig, int64_t S, int M, double* ehat, hipStream_t st);
 hipError_t launch_membership(const double* data, int64_t S, int64_t n, const double* ehat, int M, double* kme,
                              hipStream_t st);
+// Module connectivity (connectivity.hip, nr_module_connectivity): k_mod
+// [n x M, column-major] and k_total [n] (may be NULL) from the pairs in either
+// layout and slot [n] (-1 .. M - 1), all device arrays. One wave per column
+// keeps a tile of module bins in LDS, 512 bytes per module; M modules run
+// ceil(M / tile) launches over the network. connectivity_tile, a pure function
+// of M: the passes are the fewest that kConnectivityTileMax modules each
+// allow, ceil(M / 64), and the tile splits M evenly among them, ceil(M /
+// passes), so a wave holds at most 32 KiB and a CU at least five waves.
+// tile 0: that default; else 1 .. kConnectivityTileMax (a test's choice).
+constexpr int kConnectivityTileMax = 64;
+int connectivity_tile(int M);
+hipError_t launch_connectivity(const double2* pairs, int es, int64_t n, const int32_t* slot, int M, int tile,
+                               double* k_total, double* k_mod, hipStream_t st);
 // corr[e], net[e] (either may be NULL) = elements [first, first + len) of a
 // pair array in layout es (1, or 2: the Gram table).
 hipError_t launch_deinterleave(const double2* pairs, int es, int64_t first, int64_t len, double* corr, double* net,

@@ -1,15 +1,17 @@
 // Host rules that follow the eigengenes: see modmerge_host.h and the contract
-// in include/netrep_gpu.h (netrep_EigengeneGroups, netrep_MergeLabels,
-// netrep_TrimModulesKME).
+// in include/netrep_gpu.h (netrep_EigengeneGroups, netrep_EigengeneTree,
+// netrep_MergeLabels, netrep_TrimModulesKME, netrep_IntramodularConnectivity).
 #include "modmerge_host.h"
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <map>
 
 namespace nr {
 
-bool eigengene_groups(const double* eig, int64_t S, int64_t M, double cut_height, int32_t* group, double* height) {
+bool eigengene_tree(const double* eig, int64_t S, int64_t M, int linkage, int32_t* slot_lo, int32_t* slot_hi,
+                    double* height) {
   if (M < 1 || S < 2) return false;
   // centred columns and their sums of squares, every sum in sample order
   std::vector<double> z((size_t)(S * M)), ss((size_t)M);
@@ -40,7 +42,6 @@ bool eigengene_groups(const double* eig, int64_t S, int64_t M, double cut_height
   // lowest column index among its members; the other slot is retired.
   std::vector<double> size((size_t)M, 1.0);
   std::vector<char> live((size_t)M, 1);
-  for (int64_t m = 0; m < M; ++m) group[m] = (int32_t)m;
   for (int64_t step = 0; step + 1 < M; ++step) {
     int64_t bi = -1, bj = -1;
     double best = 0.0;
@@ -57,19 +58,57 @@ bool eigengene_groups(const double* eig, int64_t S, int64_t M, double cut_height
       }
     }
     height[step] = best;
+    slot_lo[step] = (int32_t)bi;
+    slot_hi[step] = (int32_t)bj;
     const double si = size[(size_t)bi], sj = size[(size_t)bj];
     for (int64_t k = 0; k < M; ++k) {
       if (!live[(size_t)k] || k == bi || k == bj) continue;
-      const double v = (si * d[(size_t)(k * M + bi)] + sj * d[(size_t)(k * M + bj)]) / (si + sj);
+      const double di = d[(size_t)(k * M + bi)], dj = d[(size_t)(k * M + bj)];
+      const double v = linkage == kLinkageComplete ? std::max(di, dj) : (si * di + sj * dj) / (si + sj);
       d[(size_t)(k * M + bi)] = d[(size_t)(bi * M + k)] = v;
     }
     size[(size_t)bi] = si + sj;
     live[(size_t)bj] = 0;
-    if (best <= cut_height)
-      for (int64_t m = 0; m < M; ++m)
-        if (group[m] == (int32_t)bj) group[m] = (int32_t)bi;
   }
   return true;
+}
+
+bool eigengene_groups(const double* eig, int64_t S, int64_t M, double cut_height, int32_t* group, double* height) {
+  std::vector<int32_t> lo((size_t)std::max<int64_t>(M - 1, 0)), hi(lo.size());
+  if (!eigengene_tree(eig, S, M, kLinkageAverage, lo.data(), hi.data(), height)) return false;
+  for (int64_t m = 0; m < M; ++m) group[m] = (int32_t)m;
+  for (int64_t step = 0; step + 1 < M; ++step)
+    if (height[step] <= cut_height)
+      for (int64_t m = 0; m < M; ++m)
+        if (group[m] == hi[(size_t)step]) group[m] = lo[(size_t)step];
+  return true;
+}
+
+void tree_slots_to_ids(int64_t M, const int32_t* slot_lo, const int32_t* slot_hi, int32_t* id_lo, int32_t* id_hi) {
+  std::vector<int32_t> id((size_t)M);
+  for (int64_t m = 0; m < M; ++m) id[(size_t)m] = (int32_t)m;
+  for (int64_t t = 0; t + 1 < M; ++t) {
+    const int32_t lo = slot_lo[t], hi = slot_hi[t];  // read first: the outputs may be the inputs
+    id_lo[t] = id[(size_t)lo];
+    id_hi[t] = id[(size_t)hi];
+    id[(size_t)lo] = (int32_t)(M + t);
+  }
+}
+
+void intramodular_connectivity(int64_t n, const int32_t* slot, const double* k_total, const double* k_mod,
+                               double* k_within, double* k_out, double* k_diff) {
+  const double na = std::numeric_limits<double>::quiet_NaN();
+  for (int64_t i = 0; i < n; ++i) {
+    if (slot[i] < 0) {
+      k_within[i] = k_out[i] = k_diff[i] = na;
+      continue;
+    }
+    const double w = k_mod[(int64_t)slot[i] * n + i];
+    const double o = k_total[i] - w;
+    k_within[i] = w;
+    k_out[i] = o;
+    k_diff[i] = w - o;
+  }
 }
 
 bool module_labels_of(int64_t n, const int32_t* labels, std::vector<int32_t>& modules) {

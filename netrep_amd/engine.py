@@ -436,6 +436,34 @@ class Engine:
         self._check(self._lib.nr_membership_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
+    def module_connectivity(self, n_mod: int, slot):
+        """Connectivity of every node of the resident network to each of
+        ``n_mod`` modules and to everything (nr_module_connectivity; the
+        summation order is stated there). ``slot``: one module index
+        0 .. n_mod - 1 per node, -1 unassigned. Returns ``(k_mod, k_total)``:
+        an ``(n_nodes, n_mod)`` Fortran-ordered array and a vector."""
+        n, _s = self.shape()
+        sl = np.ascontiguousarray(slot, dtype=np.int32)
+        if sl.shape != (n,):
+            raise ValueError("slot must hold one module index per node")
+        k_mod = np.empty((n, max(int(n_mod), 0)), dtype=np.float64, order="F")
+        k_total = np.empty(n)
+        self._check(self._lib.nr_module_connectivity(self._h, int(n_mod), _ptr(sl, C.c_int32), _ptr(k_total),
+                                                     _ptr(k_mod)))
+        return k_mod, k_total
+
+    def connectivity_ms(self) -> float:
+        """Device time in ms of the kernels of this engine's last
+        ``module_connectivity`` call (nr_connectivity_ms)."""
+        ms = C.c_double()
+        self._check(self._lib.nr_connectivity_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def set_connectivity_module_tile(self, tile: int):
+        """Test knob (nr_set_connectivity_module_tile): modules per pass of
+        later ``module_connectivity`` calls, 0 the default."""
+        self._check(self._lib.nr_set_connectivity_module_tile(self._h, int(tile)))
+
     def release_scratch(self):
         """Free the per-batch work buffers (nr_release_scratch)."""
         self._check(self._lib.nr_release_scratch(self._h))
